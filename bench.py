@@ -23,6 +23,14 @@ irradiance grid, through the C-ABI, when N > 1).  Workload at N = 1: BASELINE co
                                                         in-process only what passed on every rank: C-ABI RCCL -> torch's NCCL
                                                         group -> gloo; config.transport_probes says which)
 
+  A plain run sets up, warms up, times exactly K steps and prints the headline (value, ms_per_step) and the run's
+  configuration.  --full adds what takes runs of its own: six more timed batches, per-kernel times and the roofline, the
+  Woodcock step count, the labelled extras (other formulations, I = 4, configs 3 / 5, pipelined, ...), the CPU baseline
+  and, at N > 1, the exchange's byte counts and its self-check.
+  --dump-outputs DIR   after the timed steps: the light volume the last timed step produced (rank 0's: the summed one at
+                       N > 1) as DIR/light_volume.npy, float32 (a fixed seeded sample, light_volume_sample.npy, when larger
+                       than DUMP_LIMIT_BYTES)
+
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -395,8 +403,24 @@ def probe_in_child(kind, where, rank, world, device, budget_s):
     return False, f"rank {rank}'s probe process exited with code {p.returncode}" + (f" ({said[-1].strip()[:200]})" if said else "")
 
 
-TIMED_BATCHES = 7   # the timed region is repeated; the median batch is reported
+TIMED_BATCHES = 7   # --full: the timed region is repeated; every batch and the median one are reported beside the headline's
 MIN_WARM_STEPS = 200 # untimed frames before the first timed batch, whatever --warmup says (see main)
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # --dump-outputs: what is written in all (a larger output is sampled)
+
+
+def dump_outputs(directory, arrays):
+    """Write every array as directory/<name>.npy in float32; one larger than what is left of DUMP_LIMIT_BYTES becomes a fixed
+    sample of its elements (seeded: the same elements on every run) as <name>_sample.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > left:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, left // 4, replace=False))
+            a, name = a.reshape(-1)[keep], name + "_sample"
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def main():
@@ -446,6 +470,11 @@ def main():
     ap.add_argument("--test-one-device", action="store_true", help="(testing) every rank uses cuda:0")
     ap.add_argument("--graph", action="store_true",
                     help="replay a captured HIP graph of the frame instead of eager launches (measured slower here)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: repeated batches, per-kernel times + roofline, extras, CPU baseline, "
+                         "the exchange's byte counts and self-check (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the light volume of the last timed step to DIR/light_volume.npy (float32)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
@@ -818,17 +847,17 @@ def main():
             reducer.flush()
             ranks_barrier()
 
-    # W untimed steps, then TIMED_BATCHES batches of exactly K steps, each between two barrier + synchronize pairs and taken as the
-    # MAX over the ranks; ms_per_step / value are the MEDIAN batch's (K = 20 frames of config 2 last 1.4 ms: one batch is one sample of
-    # the box's clocks; every batch's figure is in the line)
+    # W untimed steps, then ONE batch of exactly K steps between two barrier + synchronize pairs, taken as the MAX over the ranks:
+    # ms_per_step / value.  --full repeats the batch TIMED_BATCHES - 1 times afterwards (K = 20 frames of config 2 last 1.4 ms: one
+    # batch is one sample of the box's clocks) and lists every batch beside the headline's
     for _ in range(args.warmup):
         step()
     # (a fresh box's clocks are still rising after W = 5 frames -- 0.3 ms of work: the first batches of a short run read 2 - 3 % slow.
-    # Untimed frames up to MIN_WARM_STEPS in all; the K timed steps of every batch are untouched)
+    # Untimed frames up to MIN_WARM_STEPS in all; the K timed steps are untouched)
     for _ in range(max(0, MIN_WARM_STEPS - args.warmup)):
         step()
-    batch_elapsed = []
-    for _ in range(TIMED_BATCHES):
+
+    def timed_batch():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -839,31 +868,46 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        batch_elapsed.append(dt)
-    elapsed = sorted(batch_elapsed)[len(batch_elapsed) // 2]
-    # (N > 1: the last timed frame's sum, as the exchange left it at the display GPU -- held against an independent dense sum below)
+        return dt
+    elapsed = timed_batch()
+    out_rank = 0 if root is None else root
+    # what the last timed step handed its caller: the light volume (at N > 1 the sum, as the exchange left it at the display GPU)
+    if correlated:
+        last_volume = fr.light_volume if world == 1 else total_grid
+    elif fast and world == 1:
+        last_volume = lanes[(frame_no[0] - 1) % len(lanes)][0].light_volume
+    else:
+        last_volume = reducer.result(frame_no[0] - 1)
+    if args.dump_outputs and rank == out_rank:
+        dump_outputs(args.dump_outputs, {"light_volume": last_volume.detach().cpu().numpy()})
+    # (N > 1, --full: the last timed frame's sum -- held against an independent dense sum below)
     final_sum = None
-    if world > 1 and not correlated and rank == (0 if root is None else root):
-        final_sum = reducer.result(frame_no[0] - 1).detach().clone()
+    if args.full and world > 1 and not correlated and rank == out_rank:
+        final_sum = last_volume.detach().clone()
+    batch_elapsed = [elapsed]
+    if args.full:
+        batch_elapsed += [timed_batch() for _ in range(TIMED_BATCHES - 1)]
 
-    # ---- second pass with per-kernel HIP events (library hook) on the same stream
+    # ---- --full: second pass with per-kernel HIP events (library hook) on the same stream
     prof_steps = min(args.steps, 100)
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    for _ in range(prof_steps):
-        if correlated:
-            step()
-        else:
-            fr.trace()
-            if fast:
-                fr.bin_fast(); fr.gather_fast()
+    kern = None
+    if args.full:
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        for _ in range(prof_steps):
+            if correlated:
+                step()
             else:
-                fr.bin(); fr.gather()
-    kern = ctx.profile_collect()
-    ctx.profile_enable(False)
+                fr.trace()
+                if fast:
+                    fr.bin_fast(); fr.gather_fast()
+                else:
+                    fr.bin(); fr.gather()
+        kern = ctx.profile_collect()
+        ctx.profile_enable(False)
     woodcock_steps = None
     extras = {}
-    if not correlated:
+    if args.full and not correlated:
         # one more trace with the Woodcock iteration counter on (statistics; its atomics are not timed)
         counter = torch.zeros(1, dtype=torch.int64, device="cuda")
         ctx.set_step_counter(counter)
@@ -872,10 +916,10 @@ def main():
         ctx.set_step_counter(None)
         woodcock_steps = int(counter.item())
 
-    if not correlated:
+    if args.full and not correlated:
         fr.set_planar_records(False)   # (the extras below read fr.photons as float8 records: other formulations, the identity checks)
-    # ---- labelled extras (never `value`), rank 0 of a single-GPU run only
-    if world == 1 and not args.no_extras and not correlated:
+    # ---- --full: labelled extras (never `value`), rank 0 of a single-GPU run only
+    if args.full and world == 1 and not args.no_extras and not correlated:
         reps = max(10, min(args.steps, 50))
         # the other formulations of the same frame on the same photons
         other = (lambda: (fr.trace(), fr.bin(), fr.gather())) if fast else (lambda: (fr.trace(), fr.bin_fast(), fr.gather_fast()))
@@ -1240,7 +1284,7 @@ def main():
 
     # what every rank's light volume lights, for the exchange's byte model (all ranks: the counts are gathered)
     exchange_rows = None
-    if not correlated and world > 1 and fast:
+    if args.full and not correlated and world > 1 and fast:
         tmp = torch.empty_like(fr.light_volume)
         fr.trace(); fr.bin_fast(); fr.gather_fast(out=tmp)
         lit = (sharding.brick_view(tmp, (gdim,) * 3, 1).reshape(-1, 64) != 0).any(dim=1)
@@ -1269,32 +1313,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = n_total * args.steps / elapsed / 1e6
-        per_frame = {k: (tot / prof_steps, calls / prof_steps, tot / calls) for k, (tot, calls) in kern.items()}
-
-        def stage(names):
-            return round(sum(per_frame[k][0] for k in per_frame if any(k.startswith(n) for n in names)), 4)
-
-        stages = {"trace": stage(["trace_kernel"]),
-                  "bin": stage(["bin_", "radix_", "cell_start", "fast_count", "fast_scan", "fast_scatter"]),
-                  "gather": stage(["gather", "fast_brick", "fast_halo"]),
-                  "reduce": stage(["rccl_"])}
-        tile = 256 * (4 if n_rank <= (1 << 15) else 8 if n_rank <= (1 << 23) else 16)
-        tiles = -(-n_rank // tile)
-        ab = algorithmic_bytes(n_rank, 1, vol_np.size, tf.shape[0], gdim ** 3, 1, tiles)
-        path_kernels = {k: v for k, v in per_frame.items() if k.split("<")[0].replace("cpm::", "") in ab or k.startswith("gather")}
-        dom = max(path_kernels or per_frame, key=lambda k: per_frame[k][0])
-        dom_base = dom.split("<")[0].replace("cpm::", "")
-        if dom_base.startswith("gather"):
-            dom_base = "gather_kernel"
-        dom_avg_ms = per_frame[dom][2]
-        achieved = ab.get(dom_base, 0) / (dom_avg_ms * 1e-3) / 1e9
-        if fast:
-            frame_bytes = sum(ab[k] for k in ("trace_kernel", "fast_count_kernel", "fast_scatter_kernel", "fast_brick_kernel"))
-        else:
-            passes = -(-int(gdim ** 3).bit_length() // 8)
-            frame_bytes = (ab["trace_kernel"] + ab["bin_keys_kernel"] + passes * (ab["radix_hist_kernel"] + ab["radix_rowscan_kernel"] + ab["radix_scatter_kernel"])
-                           + ab["bin_finalize_kernel"] + ab["cell_start_kernel"] + ab["gather_kernel"])
-        traffic, traffic_src = pmc_traffic(dom.split("<")[0], args.workload)
         what = {"fast": "brick bin + one-launch fixed-point LDS-tile gather (cpm_bin_fast + cpm_gather_fast: tolerance mode, rtol 2e-5 / atol 1e-5 max "
                         "vs the reference semantics, bitwise reproducible)",
                 "exact": "cell sort + sequential per-voxel gather (cpm_bin + cpm_gather: bit-exact contract)"}[args.formulation]
@@ -1305,10 +1323,13 @@ def main():
             "warmup": max(args.warmup, MIN_WARM_STEPS), "warmup_requested": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "timing": {"what": f"median of {TIMED_BATCHES} timed batches of {args.steps} steps each (every batch between barrier + synchronize pairs, "
-                               "MAX over ranks); value and ms_per_step are that batch's; untimed frames before the first batch: "
-                               f"{max(args.warmup, MIN_WARM_STEPS)} (--warmup {args.warmup}, at least {MIN_WARM_STEPS}: a fresh box's clocks are still rising after 5)",
-                       "batch_ms_per_step": [round(e / args.steps * 1e3, 4) for e in batch_elapsed]},
+            "timing": {"what": f"one timed batch of {args.steps} steps (between barrier + synchronize pairs, MAX over ranks); value and ms_per_step "
+                               f"are that batch's; untimed frames before it: {max(args.warmup, MIN_WARM_STEPS)} (--warmup {args.warmup}, at least "
+                               f"{MIN_WARM_STEPS}: a fresh box's clocks are still rising after 5)"
+                               + (f"; --full: {TIMED_BATCHES - 1} more batches after it, every batch listed (the headline's first)" if args.full else ""),
+                       "batch_ms_per_step": [round(e / args.steps * 1e3, 4) for e in batch_elapsed],
+                       **({"median_batch_ms_per_step": round(sorted(batch_elapsed)[len(batch_elapsed) // 2] / args.steps * 1e3, 4)}
+                          if args.full else {})},
             "config": {"workload": (f"BASELINE {args.workload}: {vdim}^3 u8 heterogeneous volume, {n_total} photons per frame in all "
                                     f"({lattice[0]}x{lattice[1]} lattice, one directional light; {n_rank} on rank 0), {gdim}^3 x1 f32 light volume, "
                                     f"I=1, r=1 voxel, MWC64X streams from glibc srand(0)"
@@ -1342,25 +1363,52 @@ def main():
                        # (cpm_comm_size; 0 = the reduce did not go through the C-ABI's RCCL communicator)
                        "transport": type(transport).__name__,
                        "rccl_ranks": transport.comm.size if rccl else 0, **({"transport_probes": probes} if probes else {})},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         # also against what a copy kernel reaches on this part (6.29 TB/s, MI355X_MICROARCH.md)
-                         "copy_ceiling": HBM_COPY_GBS, "frac_of_copy_ceiling": round(achieved / HBM_COPY_GBS, 5),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": ab.get(dom_base, 0), "avg_launch_ms": round(dom_avg_ms, 5),
-                         "launches_per_frame": round(per_frame[dom][1], 2)},
-            "frame": {"kernel_ms_per_frame": {k: round(v[0], 5) for k, v in sorted(per_frame.items(), key=lambda kv: -kv[1][0])},
-                      "stage_ms": stages, "sum_kernel_ms": round(sum(v[0] for v in per_frame.values()), 4),
-                      "kernel_times_from": "a second pass of the same frames with a HIP-event pair around every launch (about 1 us more per launch "
-                                           "than in the timed region: sum_kernel_ms exceeds ms_per_step by that)",
-                      "algorithmic_bytes_per_frame": frame_bytes,
-                      "frame_hbm_frac": round(frame_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
         }
+        if args.full:
+            per_frame = {k: (tot / prof_steps, calls / prof_steps, tot / calls) for k, (tot, calls) in kern.items()}
+
+            def stage(names):
+                return round(sum(per_frame[k][0] for k in per_frame if any(k.startswith(n) for n in names)), 4)
+
+            stages = {"trace": stage(["trace_kernel"]),
+                      "bin": stage(["bin_", "radix_", "cell_start", "fast_count", "fast_scan", "fast_scatter"]),
+                      "gather": stage(["gather", "fast_brick", "fast_halo"]),
+                      "reduce": stage(["rccl_"])}
+            tile = 256 * (4 if n_rank <= (1 << 15) else 8 if n_rank <= (1 << 23) else 16)
+            tiles = -(-n_rank // tile)
+            ab = algorithmic_bytes(n_rank, 1, vol_np.size, tf.shape[0], gdim ** 3, 1, tiles)
+            path_kernels = {k: v for k, v in per_frame.items() if k.split("<")[0].replace("cpm::", "") in ab or k.startswith("gather")}
+            dom = max(path_kernels or per_frame, key=lambda k: per_frame[k][0])
+            dom_base = dom.split("<")[0].replace("cpm::", "")
+            if dom_base.startswith("gather"):
+                dom_base = "gather_kernel"
+            dom_avg_ms = per_frame[dom][2]
+            achieved = ab.get(dom_base, 0) / (dom_avg_ms * 1e-3) / 1e9
+            if fast:
+                frame_bytes = sum(ab[k] for k in ("trace_kernel", "fast_count_kernel", "fast_scatter_kernel", "fast_brick_kernel"))
+            else:
+                passes = -(-int(gdim ** 3).bit_length() // 8)
+                frame_bytes = (ab["trace_kernel"] + ab["bin_keys_kernel"] + passes * (ab["radix_hist_kernel"] + ab["radix_rowscan_kernel"] + ab["radix_scatter_kernel"])
+                               + ab["bin_finalize_kernel"] + ab["cell_start_kernel"] + ab["gather_kernel"])
+            traffic, traffic_src = pmc_traffic(dom.split("<")[0], args.workload)
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5),
+                               # also against what a copy kernel reaches on this part (6.29 TB/s, MI355X_MICROARCH.md)
+                               "copy_ceiling": HBM_COPY_GBS, "frac_of_copy_ceiling": round(achieved / HBM_COPY_GBS, 5),
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": ab.get(dom_base, 0), "avg_launch_ms": round(dom_avg_ms, 5),
+                               "launches_per_frame": round(per_frame[dom][1], 2)}
+            out["frame"] = {"kernel_ms_per_frame": {k: round(v[0], 5) for k, v in sorted(per_frame.items(), key=lambda kv: -kv[1][0])},
+                            "stage_ms": stages, "sum_kernel_ms": round(sum(v[0] for v in per_frame.values()), 4),
+                            "kernel_times_from": "a second pass of the same frames with a HIP-event pair around every launch (about 1 us more per launch "
+                                                 "than in the timed region: sum_kernel_ms exceeds ms_per_step by that)",
+                            "algorithmic_bytes_per_frame": frame_bytes,
+                            "frame_hbm_frac": round(frame_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
         if woodcock_steps is not None:
             out["frame"]["woodcock_steps_per_frame"] = woodcock_steps
             out["frame"]["gsamples_per_s"] = round(woodcock_steps / max(stages["trace"], 1e-9) / 1e6, 3)
         if correlated:
-            out["frame"]["fraction_retraced"] = round(float(np.mean(fractions[-args.steps:])), 5)
+            out.setdefault("frame", {})["fraction_retraced"] = round(float(np.mean(fractions[-args.steps:])), 5)
         infos = None
         if correlated and reduce_info:
             infos = [{"n_union": i.n_union, "capacity": i.capacity, "mode": i.mode, "reduce_bytes": i.reduce_bytes, "dense_bytes": i.dense_bytes,
@@ -1384,6 +1432,9 @@ def main():
                              "reduce_bytes_per_frame": int(max(r[1] for r in pr)),   # the busiest link: a sender's one segment
                              "exchanges_repeated_at_exact_size": int(sum(r[3] for r in pr[1:])),
                              "dense_bytes": gdim ** 3 * 4, "n_bricks": exchange_rows["n_bricks"], "stream_synchronisations_per_frame": 0}
+        elif world > 1 and not correlated and reducer.lists:   # (a plain run: the per-rank byte counts are --full's)
+            out["reduce"] = {"kind": "brick lists: every rank's own non-zero 4x4x4 bricks to rank 0 (cpm_reduce_grid_bricklists)",
+                             "dense_bytes": gdim ** 3 * 4, "stream_synchronisations_per_frame": 0}
         elif world > 1:
             out["reduce"] = {"kind": "dense", "reduce_bytes_per_frame": gdim ** 3 * 4, "dense_bytes": gdim ** 3 * 4}
         if exchange_rows and "self_check" in exchange_rows:
@@ -1399,7 +1450,7 @@ def main():
                                                "counts: messages x latency + bytes / link rate, with the constants under `constants` -- measured at set-up "
                                                "(`measured`: a 1 KB and a 2 MB ping-pong over the communicator) when the C-ABI transport ran, else assumed")
         out.update(extras)
-        if world == 1 and not args.no_cpu_baseline and not correlated:
+        if args.full and world == 1 and not args.no_cpu_baseline and not correlated:
             out["cpu_baseline"] = cpu_baseline(args.workload, vol_np, tf, lattice, gdim)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -150,3 +150,23 @@ def test_a_probe_process_reports_how_it_ended(monkeypatch):
     t0 = time.time()
     ok, why = bench.probe_in_child("cabi", "00" * 128, 1, 2, 0, 0.05)     # (still importing when the budget ends)
     assert not ok and why == "rank 1's probe process did not finish in 0 s and was killed" and time.time() - t0 < 30
+
+
+def test_dump_outputs_writes_float32_and_samples_what_is_too_large(tmp_path, monkeypatch):
+    """--dump-outputs: an array within the limit is written whole as float32; a larger one as a fixed seeded sample of its elements
+    (the same elements on every run), and never more than the limit in all."""
+    import numpy as np
+    sys.path.insert(0, str(REPO))
+    import importlib
+    bench = importlib.import_module("bench")
+    small = np.arange(1000, dtype=np.float64).reshape(10, 100)
+    bench.dump_outputs(str(tmp_path / "a"), {"light_volume": small})
+    got = np.load(tmp_path / "a" / "light_volume.npy")
+    assert got.dtype == np.float32 and got.shape == (10, 100) and np.array_equal(got, small.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 256)
+    big = np.random.default_rng(7).random(10_000).astype(np.float32)
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), {"light_volume": big})
+    b, c = np.load(tmp_path / "b" / "light_volume_sample.npy"), np.load(tmp_path / "c" / "light_volume_sample.npy")
+    assert b.dtype == np.float32 and b.nbytes <= 4 * 256 and b.size == 256 and np.array_equal(b, c)
+    assert np.isin(b, big).all()

@@ -21,7 +21,8 @@ def _last_json(out):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "10", "--warmup", "2", "--workload", "config1", "--streams", "2"],
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "10", "--warmup", "2", "--workload", "config1", "--streams", "2",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=str(REPO))
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -38,11 +39,31 @@ def test_bench_single_gpu_line():
     assert sp["n_union"] <= sp["n_bricks_4x4x4"] and sp["reduce_bytes_per_frame"] > 0 and sp["dense_bytes"] == 32 ** 3 * 4
 
 
+def test_bench_plain_line_times_exactly_its_steps_and_dumps_the_light_volume(tmp_path):
+    """A plain run (no --full): the headline alone, ONE batch of exactly --steps timed steps, nothing that needs runs of its own; and
+    --dump-outputs writes the last timed step's light volume -- the same bits on a second run with the same arguments."""
+    import numpy as np
+    vols = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "7", "--warmup", "2", "--workload", "config1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=900, cwd=str(REPO))
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _last_json(r.stdout)
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "config"} <= set(d)
+        assert d["steps"] == 7 and len(d["timing"]["batch_ms_per_step"]) == 1 and d["ms_per_step"] == d["timing"]["batch_ms_per_step"][0]
+        assert not {"roofline", "frame", "cpu_baseline", "pipelined", "other_formulation", "i4"} & set(d)
+        assert abs(d["value"] * d["ms_per_step"] * 1e3 / 65536 - 1) < 0.05    # (ms_per_step is rounded to 0.1 us)
+        v = np.load(tmp_path / run / "light_volume.npy")
+        assert v.dtype == np.float32 and v.size == 32 ** 3 and np.isfinite(v).all() and v.sum() > 0
+        vols.append(v)
+    assert np.array_equal(vols[0].view(np.uint32), vols[1].view(np.uint32))
+
+
 def test_bench_two_ranks_code_path():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", str(REPO / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--workload", "config1",
-           "--test-backend", "gloo", "--test-one-device", "--exchange", "union"]
+           "--test-backend", "gloo", "--test-one-device", "--exchange", "union", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     d = _last_json(r.stdout)
@@ -65,7 +86,7 @@ def test_bench_plain_command_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                              "TORCHELASTIC_RUN_ID")}
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--workload", "config1",
-           "--test-backend", "gloo", "--test-one-device"]
+           "--test-backend", "gloo", "--test-one-device", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -84,7 +105,7 @@ def test_bench_strong_scaling_and_exact_formulation():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29534", str(REPO / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", "config1",
-           "--scaling", "strong", "--formulation", "exact", "--test-backend", "gloo", "--test-one-device"]
+           "--scaling", "strong", "--formulation", "exact", "--test-backend", "gloo", "--test-one-device", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     d = _last_json(r.stdout)
@@ -135,7 +156,7 @@ def test_bench_two_ranks_brick_lists_through_the_c_abi():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", CPM_RCCL_LIBRARY=str(fake_build.build()))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29537", str(REPO / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--workload", "config1",
-           "--scaling", "strong", "--test-backend", "gloo", "--test-one-device", "--transport", "rccl"]
+           "--scaling", "strong", "--test-backend", "gloo", "--test-one-device", "--transport", "rccl", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     d = _last_json(r.stdout)
@@ -160,7 +181,7 @@ def test_bench_two_ranks_brick_lists_over_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29538", str(REPO / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "3", "--workload", "config1",
-           "--scaling", "strong", "--test-backend", "gloo", "--test-one-device"]
+           "--scaling", "strong", "--test-backend", "gloo", "--test-one-device", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     d = _last_json(r.stdout)
@@ -178,7 +199,7 @@ def test_bench_four_ranks_weak_scaling_chooses_its_exchange():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", CPM_RCCL_LIBRARY=str(fake_build.build()))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", "29539", str(REPO / "bench.py"), "--gpus", "4", "--steps", "5", "--warmup", "3", "--workload", "config1",
-           "--test-backend", "gloo", "--test-one-device", "--transport", "rccl"]
+           "--test-backend", "gloo", "--test-one-device", "--transport", "rccl", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     d = _last_json(r.stdout)
@@ -210,7 +231,7 @@ def test_bench_two_frames_in_flight():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", CPM_RCCL_LIBRARY=str(fake_build.build()), CPM_BENCH_RCCL_PROBE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", str(REPO / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--workload", "config1",
-           "--scaling", "strong", "--test-backend", "gloo", "--test-one-device", "--transport", "rccl", "--frames-in-flight", "2"]
+           "--scaling", "strong", "--test-backend", "gloo", "--test-one-device", "--transport", "rccl", "--frames-in-flight", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     d = _last_json(r.stdout)

@@ -3,12 +3,14 @@ versions, the processors / ports / data formats each registers, and that every p
 workspace instantiates can be created by class identifier with the port and property ids the workspace binds.
 No GPU needed (nothing is evaluated)."""
 import ctypes as C
-import re
+import json
 from pathlib import Path
 
 import pytest
 
-REF_WORKSPACE = Path("/root/reference/workspaces/CorrelatedPhotonMappingSingleVolume.inv")
+# what the reference's workspace CorrelatedPhotonMappingSingleVolume.inv instantiates: processor types with the port and property
+# identifiers each serialises (tests/golden/make_workspace_surface.py extracts them from the .inv)
+WORKSPACE_SURFACE = Path(__file__).resolve().parent / "golden" / "workspace_surface.json"
 
 MODULES = {  # ref <name>module.cpp: identifier, getVersion(), registerProcessor<...>
     "ProgressivePhotonMapping": (0, {"org.inviwo.PhotonToLightVolumeProcessorCL", "org.inviwo.ProgressivePhotonTracerCL"}),
@@ -90,28 +92,26 @@ def test_factory_creates_processors_by_class_identifier(host):
     assert host.cpmh_factory_create(b"org.inviwo.NoSuchProcessor") == b""
 
 
-@pytest.mark.skipif(not REF_WORKSPACE.exists(), reason="reference workspace not present (GPU box)")
 def test_reference_workspace_processors_are_creatable(host):
     """Every processor of the reference's own modules that CorrelatedPhotonMappingSingleVolume.inv instantiates is
     registered, and offers every port identifier the workspace connects."""
-    text = REF_WORKSPACE.read_text(errors="ignore")
+    surface = json.loads(WORKSPACE_SURFACE.read_text())
     ours = set().union(*(p for _, p in MODULES.values()))
-    blocks = re.findall(r'<Processor type="(org\.inviwo\.[A-Za-z0-9]+)".*?</Processor>', text, flags=re.S)
-    used = set(re.findall(r'<Processor type="(org\.inviwo\.[A-Za-z0-9]+)"', text))
+    used = set(surface["processor_types"])
     assert {"org.inviwo.ProgressivePhotonTracerCL", "org.inviwo.PhotonToLightVolumeProcessorCL", "org.inviwo.DirectionalLightSamplerCL",
             "org.inviwo.UniformSampleGenerator2DCL", "org.inviwo.MinMaxUniformGrid3DImportanceCLProcessor",
             "org.inviwo.VolumeMinMaxCLProcessor"} <= used
-    for m in re.finditer(r'<Processor type="(org\.inviwo\.[A-Za-z0-9]+)"(.*?)</Processor>', text, flags=re.S):
-        cid, body = m.group(1), m.group(2)
+    assert {p["type"] for p in surface["processors"]} == used
+    for proc in surface["processors"]:
+        cid = proc["type"]
         if cid not in ours:
             continue  # Inviwo's own processors (VolumeSource, raycaster, canvas, ...)
         line = host.cpmh_factory_create(cid.encode()).decode()
         assert line, cid
         _, ins, outs, props = _parse(line)
         for kind, have in (("InPort", ins), ("OutPort", outs)):
-            for ident in re.findall(r'<%s type="[^"]*" identifier="([^"]+)"' % kind, body):
+            for ident in proc[kind]:
                 assert ident in have, (cid, kind, ident)
         # every property identifier the workspace serialises for this processor (composites' members included)
-        for ident in re.findall(r'<Property type="[^"]*" identifier="([^"]+)"', body):
+        for ident in proc["Property"]:
             assert ident in props, (cid, "Property", ident)
-    assert blocks is not None

@@ -1,10 +1,29 @@
 """The oracle against the reference: golden vectors produced by the reference's own OpenCL C
 kernels (tests/golden/ref_kernels.npz, generator tests/golden/make_golden.py) and, where
-oracle/_ref exists, those kernels themselves."""
+oracle/_ref exists, those kernels themselves -- elsewhere the outputs they gave for the live tests'
+own inputs (tests/golden/ref_live.npz, generator tests/golden/make_ref_live.py)."""
 import ctypes
+from pathlib import Path
 
 import numpy as np
 import pytest
+
+REF_LIVE = Path(__file__).resolve().parent / "golden" / "ref_live.npz"
+
+
+@pytest.fixture(scope="module")
+def live():
+    """live(name, compute, lib2=False) -> the reference kernels' outputs for test `name`: compute(Ref()) where oracle/_ref was built
+    (libcpm_ref2.so too when lib2), else what compute returned when ref_live.npz was made."""
+    from oracle_binding import Ref, REF_LIB
+    ref = Ref() if REF_LIB.exists() else None
+    stored = np.load(REF_LIVE)
+
+    def get(name, compute, lib2=False):
+        if ref is not None and (ref.lib2 is not None or not lib2):
+            return compute(ref)
+        return {k.split("/", 1)[1]: stored[k] for k in stored.files if k.startswith(name + "/")}
+    return get
 
 
 def test_glibc_rand_bases(oracle, golden):
@@ -67,23 +86,42 @@ def test_threshold_count_iota_golden(oracle, golden):
     assert np.array_equal(imp, golden["threshold_in"][order])
 
 
-def test_live_reference_rng(oracle, ref):
+def _rng_input():
     rng = np.random.default_rng(7)
     n = 3000
     st = np.zeros((n, 2), np.uint32)
     st[:, 0] = rng.integers(0, 2**31, n)
-    a, b = st.copy(), st.copy()
-    oracle.seed_streams(a, 1 << 40)
+    return st
+
+
+def rng_reference(ref):
+    b = _rng_input()
     ref.generate_random_state(b)
-    assert np.array_equal(a, b)
-    oa = oracle.random_fill(a, 16)
+    seeded = b.copy()
     ob, _ = ref.random_fill(b, 16)
-    assert np.array_equal(oa.view(np.uint32), ob.view(np.uint32)) and np.array_equal(a, b)
+    return {"seeded": seeded, "draws": ob, "state_after": b}
 
 
-def test_live_reference_density_kernel(oracle, ref):
-    x = np.random.default_rng(3).random(20000, dtype=np.float32) * np.float32(1.2)
-    want = ref.density_kernel(x)
+def test_live_reference_rng(oracle, live):
+    want = live("rng", rng_reference)
+    a = _rng_input()
+    oracle.seed_streams(a, 1 << 40)
+    assert np.array_equal(a, want["seeded"])
+    oa = oracle.random_fill(a, 16)
+    assert np.array_equal(oa.view(np.uint32), want["draws"].view(np.uint32)) and np.array_equal(a, want["state_after"])
+
+
+def _density_input():
+    return np.random.default_rng(3).random(20000, dtype=np.float32) * np.float32(1.2)
+
+
+def density_reference(ref):
+    return {"y": ref.density_kernel(_density_input())}
+
+
+def test_live_reference_density_kernel(oracle, live):
+    x = _density_input()
+    want = live("density", density_reference)["y"]
     got = np.array([oracle.lib.cpmo_density_kernel(float(v)) for v in x], np.float32)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
@@ -101,15 +139,29 @@ def test_mix_kernel_golden(oracle, golden):
     assert np.array_equal(golden["mix_u16x2"][0], golden["mix_ux"])
 
 
-def test_live_reference_mix_kernel(oracle, ref):
+MIX_A = (0.0, 0.1, 0.5, 0.73, 1.0)
+
+
+def _mix_input():
     rng = np.random.default_rng(11)
     x = (rng.standard_normal(5000) * 100).astype(np.float32)
     y = (rng.standard_normal(5000) * 100).astype(np.float32)
     ux = rng.integers(0, 65536, (3001, 2)).astype(np.uint16)
     uy = rng.integers(0, 65536, (3001, 2)).astype(np.uint16)
-    for a in (0.0, 0.1, 0.5, 0.73, 1.0):
-        assert np.array_equal(oracle.mix_f32(x, y, a).view(np.uint32), ref.mix_f32(x, y, a).view(np.uint32))
-        assert np.array_equal(oracle.mix_u16x2(ux, uy, a), ref.mix_u16x2(ux, uy, a))
+    return x, y, ux, uy
+
+
+def mix_reference(ref):
+    x, y, ux, uy = _mix_input()
+    return {"f32": np.stack([ref.mix_f32(x, y, a) for a in MIX_A]), "u16x2": np.stack([ref.mix_u16x2(ux, uy, a) for a in MIX_A])}
+
+
+def test_live_reference_mix_kernel(oracle, live):
+    x, y, ux, uy = _mix_input()
+    want = live("mix", mix_reference)
+    for k, a in enumerate(MIX_A):
+        assert np.array_equal(oracle.mix_f32(x, y, a).view(np.uint32), want["f32"][k].view(np.uint32))
+        assert np.array_equal(oracle.mix_u16x2(ux, uy, a), want["u16x2"][k])
 
 
 def test_random_number_kernel_golden(oracle, golden):
@@ -145,18 +197,28 @@ def test_copy_indexed_photons_reads_the_reference_layout(oracle, golden):
     assert np.array_equal(out[~sent].view(np.uint32), want[~sent].view(np.uint32))
 
 
-def test_live_reference_random_number_kernel_and_photon_records(oracle, ref):
-    if ref.lib2 is None:
-        pytest.skip("oracle/_ref/libcpm_ref2.so not built")
+def _rng_kernel_input(oracle):
     rng = np.random.default_rng(21)
     st = np.zeros((777, 2), np.uint32)
     st[:, 0] = rng.integers(0, 2**31, 777)
     oracle.seed_streams(st, 1 << 40)
-    a, b = st.copy(), st.copy()
-    for _ in range(5):
-        assert np.array_equal(oracle.random_fill(a, 1)[0].view(np.uint32), ref.random_number_kernel(b).view(np.uint32))
-    assert np.array_equal(a, b)
     ph = rng.standard_normal((100, 8)).astype(np.float32)
     ids = rng.permutation(128)[:100].astype(np.int32)
+    return st, ph, ids
+
+
+def rng_kernel_reference(ref, oracle):
+    b, ph, ids = _rng_kernel_input(oracle)
+    draws = np.stack([ref.random_number_kernel(b) for _ in range(5)])
     buf, back = ref.photon_write_read(ph, ids, 128)
+    return {"draws": draws, "state_after": b, "photon_buffer": buf, "photon_read_back": back}
+
+
+def test_live_reference_random_number_kernel_and_photon_records(oracle, live):
+    a, ph, ids = _rng_kernel_input(oracle)
+    want = live("rng_kernel", lambda ref: rng_kernel_reference(ref, oracle), lib2=True)
+    for k in range(5):
+        assert np.array_equal(oracle.random_fill(a, 1)[0].view(np.uint32), want["draws"][k].view(np.uint32))
+    assert np.array_equal(a, want["state_after"])
+    buf, back = want["photon_buffer"], want["photon_read_back"]
     assert np.array_equal(buf[ids], ph) and np.array_equal(back, ph)

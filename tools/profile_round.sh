@@ -20,5 +20,5 @@ rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY S
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $O/sq_c -- python3 tools/stage_only.py frame_fast 10 $WL > $O/sq_c.log 2>&1
 mkdir -p $O/sq; cp -r $O/sq_a $O/sq/a; cp -r $O/sq_b $O/sq/b; cp -r $O/sq_c $O/sq/c
 python3 tools/pmc_summary.py $O/sq > $O/sq_counters_summary.txt
-python3 bench.py --workload $WL --steps 200 --warmup 20 > $O/bench.log 2>&1; grep '"metric"' $O/bench.log > $O/bench.json; cut -c1-600 $O/bench.json
+python3 bench.py --workload $WL --steps 200 --warmup 20 --full > $O/bench.log 2>&1; grep '"metric"' $O/bench.log > $O/bench.json; cut -c1-600 $O/bench.json
 rm -rf $O/stats $O/pmc_fetch $O/pmc_write $O/sq_a $O/sq_b $O/sq_c $O/sq
