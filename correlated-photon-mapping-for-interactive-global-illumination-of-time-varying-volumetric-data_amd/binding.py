@@ -46,7 +46,9 @@ EXT_SYMBOLS = [
     "cpm_photon_importance_select", "cpm_photon_importance_retrace", "cpm_photon_importance_retrace_lights", "cpm_photon_importance_equal_select",
     "cpm_selection_finish", "cpm_selection_set_occupancy", "cpm_selection_count_device", "cpm_selection_count", "cpm_trace_selected", "cpm_splat_delta",
     "cpm_pinned_alloc", "cpm_pinned_free", "cpm_volume_stream_create", "cpm_volume_stream_destroy", "cpm_volume_stream_prefetch",
-    "cpm_volume_stream_acquire", "cpm_volume_stream_stats", "cpm_allreduce_grid_bricks", "cpm_brick_mask_or", "cpm_sparse_reduce_create",
+    "cpm_volume_stream_acquire", "cpm_volume_stream_stats", "cpm_sequence_delta_encode", "cpm_sequence_delta_create",
+    "cpm_sequence_delta_get_info", "cpm_sequence_delta_transition", "cpm_sequence_delta_destroy", "cpm_volume_stream_use_delta",
+    "cpm_volume_stream_delta_stats", "cpm_allreduce_grid_bricks", "cpm_brick_mask_or", "cpm_sparse_reduce_create",
     "cpm_sparse_reduce_destroy", "cpm_sparse_reduce_bricks", "cpm_sparse_reduce_capacity_for", "cpm_allreduce_grid_sparse", "cpm_sparse_reduce_complete",
     "cpm_bricklist_reduce_create", "cpm_bricklist_reduce_destroy", "cpm_bricklist_reduce_bricks", "cpm_bricklist_capacity_for",
     "cpm_bricklist_segment_bytes", "cpm_reduce_grid_bricklists", "cpm_bricklist_reduce_complete", "cpm_bricklist_reduce_open", "cpm_bricklist_pack_grid",
@@ -160,6 +162,19 @@ class VolumeStreamInfo(C.Structure):
     """cpm_volume_stream_info"""
     _fields_ = [("uploads", C.c_uint64), ("hits", C.c_uint64), ("uploads_at_acquire", C.c_uint64), ("bytes_uploaded", C.c_uint64),
                 ("bytes_per_step", C.c_uint64), ("uploads_timed", C.c_uint64), ("upload_ms_total", C.c_double)]
+
+
+class SequenceDeltaInfo(C.Structure):
+    """cpm_sequence_delta_info"""
+    _fields_ = [("n_steps", C.c_int32), ("n_transitions", C.c_int32), ("n_delta_transitions", C.c_int32), ("wrap", C.c_int32),
+                ("step_bytes", C.c_uint64), ("delta_bytes_total", C.c_uint64), ("delta_bytes_max", C.c_uint64),
+                ("dirty_fraction", C.c_double), ("analysis_ms", C.c_double)]
+
+
+class VolumeStreamDeltaInfo(C.Structure):
+    """cpm_volume_stream_delta_info"""
+    _fields_ = [("delta_uploads", C.c_uint64), ("full_uploads", C.c_uint64), ("delta_bytes", C.c_uint64), ("full_bytes", C.c_uint64),
+                ("delta_uploads_timed", C.c_uint64), ("delta_h2d_ms_total", C.c_double)]
 
 
 class BricklistSegment(C.Structure):
@@ -327,6 +342,13 @@ def load_library() -> C.CDLL:
         "cpm_volume_stream_prefetch": (i32, [vp, vp, C.c_uint64, vp, vp]),
         "cpm_volume_stream_acquire": (i32, [vp, vp, C.c_uint64, vp, vp, P(vp)]),
         "cpm_volume_stream_stats": (i32, [vp, vp, P(VolumeStreamInfo)]),
+        "cpm_sequence_delta_encode": (i32, [P(VolumeDesc), vp, vp, vp, vp, sz, P(u32), P(sz)]),
+        "cpm_sequence_delta_create": (i32, [vp, P(VolumeDesc), P(vp), i32, i32, P(vp)]),
+        "cpm_sequence_delta_get_info": (i32, [vp, vp, P(SequenceDeltaInfo)]),
+        "cpm_sequence_delta_transition": (i32, [vp, vp, i32, i32, P(u32), P(u64)]),
+        "cpm_sequence_delta_destroy": (None, [vp, vp]),
+        "cpm_volume_stream_use_delta": (i32, [vp, vp, vp]),
+        "cpm_volume_stream_delta_stats": (i32, [vp, vp, P(VolumeStreamDeltaInfo)]),
         "cpm_gl_available": (i32, [vp]),
         "cpm_gl_register_buffer": (i32, [vp, u32, i32, P(vp)]),
         "cpm_light_volume_texels": (i32, [vp, vp, sz, i32, vp, vp]),
@@ -1118,6 +1140,71 @@ class PinnedSequence:
             pass
 
 
+def _volume_desc_like(like):
+    import numpy as np
+    code = {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32}[np.dtype(like.dtype)]
+    return default_volume_desc(like.shape[::-1], code)
+
+
+def sequence_delta_encode(from_arr, to_arr):
+    """cpm_sequence_delta_encode (pure host code, no GPU): the changed 16-byte pieces of to_arr against from_arr (same shape [z, y, x] and
+    type) -> (runs uint32[n, 3] of (first_piece, n_pieces, payload_piece_offset), payload bytes)."""
+    import numpy as np
+    a, b = np.ascontiguousarray(from_arr), np.ascontiguousarray(to_arr)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        raise ValueError("the two steps differ in shape or type")
+    lib = load_library()
+    desc = _volume_desc_like(a)
+    n_runs, pay = C.c_uint32(), C.c_size_t()
+    rc = lib.cpm_sequence_delta_encode(C.byref(desc), a.ctypes.data, b.ctypes.data, None, None, 0, C.byref(n_runs), C.byref(pay))
+    if rc != CPM_OK:
+        raise CpmError(rc, "cpm_sequence_delta_encode")
+    runs = np.zeros((n_runs.value, 3), np.uint32)
+    payload = np.zeros(max(pay.value, 1), np.uint8)
+    rc = lib.cpm_sequence_delta_encode(C.byref(desc), a.ctypes.data, b.ctypes.data, runs.ctypes.data, payload.ctypes.data, pay.value,
+                                       C.byref(n_runs), C.byref(pay))
+    if rc != CPM_OK:
+        raise CpmError(rc, "cpm_sequence_delta_encode")
+    return runs, payload[:pay.value].tobytes()
+
+
+class SequenceDelta:
+    """cpm_sequence_delta: the host pre-pass over a sequence (what changes at every transition t -> t + 1, and n - 1 -> 0 with wrap) that a
+    VolumeStream uploads instead of whole steps (use_delta).  steps: numpy arrays [z, y, x] or a PinnedSequence."""
+
+    def __init__(self, ctx: Context, steps, wrap: bool = True):
+        import numpy as np
+        self.ctx = ctx
+        arrays = list(steps.steps) if isinstance(steps, PinnedSequence) else [np.ascontiguousarray(v) for v in steps]
+        self.desc = _volume_desc_like(arrays[0])
+        ptrs = (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.cpm_sequence_delta_create(ctx.h, C.byref(self.desc), ptrs, len(arrays), int(bool(wrap)), C.byref(self.h)))
+
+    def info(self) -> SequenceDeltaInfo:
+        info = SequenceDeltaInfo()
+        self.ctx._check(self.ctx.lib.cpm_sequence_delta_get_info(self.ctx.h, self.h, C.byref(info)))
+        return info
+
+    def transition(self, a: int, b: int):
+        """(runs, bytes) of the forward transition a -> b; (0, the step's bytes) when it uploads in full."""
+        n, nbytes = C.c_uint32(), C.c_uint64()
+        self.ctx._check(self.ctx.lib.cpm_sequence_delta_transition(self.ctx.h, self.h, a, b, C.byref(n), C.byref(nbytes)))
+        return n.value, nbytes.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.cpm_sequence_delta_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
 class VolumeStream:
     """cpm_volume_stream: a ring of device volumes over a host-resident sequence, uploads on the library's copy stream (cpm.h)."""
 
@@ -1153,6 +1240,17 @@ class VolumeStream:
     def stats(self) -> VolumeStreamInfo:
         info = VolumeStreamInfo()
         self.ctx._check(self.ctx.lib.cpm_volume_stream_stats(self.ctx.h, self.h, C.byref(info)))
+        return info
+
+    def use_delta(self, delta: SequenceDelta):
+        """Upload only what changed since the step before when that step is resident (cpm_volume_stream_use_delta); tags become the delta's
+        step indices.  Before the first prefetch / acquire."""
+        self.ctx._check(self.ctx.lib.cpm_volume_stream_use_delta(self.ctx.h, self.h, delta.h))
+        self.delta = delta
+
+    def delta_stats(self) -> VolumeStreamDeltaInfo:
+        info = VolumeStreamDeltaInfo()
+        self.ctx._check(self.ctx.lib.cpm_volume_stream_delta_stats(self.ctx.h, self.h, C.byref(info)))
         return info
 
     def close(self):

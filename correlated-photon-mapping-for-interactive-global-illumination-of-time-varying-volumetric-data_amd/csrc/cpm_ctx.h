@@ -94,6 +94,22 @@ struct cpm_volume {
     size_t bytes = 0;
 };
 
+// cpm_sequence_delta_create's result (include/cpm/cpm_ext.h): per forward transition `from` -> from + 1 (mod n_steps with wrap) one block in
+// pinned host memory -- the run table rounded up to 16 bytes, then the payload -- or none ("full").  Shared by the streams it is attached to.
+struct cpm_sequence_delta {
+    struct Transition {
+        void* block = nullptr;        // pinned; nullptr: full (or identical steps: n_runs == 0, bytes == 0, stored)
+        bool stored = false;
+        uint32_t n_runs = 0;
+        uint64_t payload_bytes = 0, bytes = 0;
+    };
+    cpm_volume_desc desc;
+    int n_steps = 0, wrap = 0, refs = 1;
+    uint64_t step_bytes = 0;
+    std::vector<Transition> transitions;   // [from]
+    double dirty_fraction = 0.0, analysis_ms = 0.0;
+};
+
 struct cpm_tf {
     int width = 0;
     float* rgba = nullptr;   // device, width * 4
@@ -116,6 +132,8 @@ bool affine_from_matrix(const float m[16], Affine& out);
 // rebuild vol->quads from `src` (a device block laid out like vol->voxels; vol->voxels itself, or the source of a
 // device->device update, which is then also copied into vol->voxels by the same launch)
 int build_quads(cpm_ctx* ctx, cpm_volume* vol, const void* src, bool copy_linear, hipStream_t stream);
+// apply a delta block (cpm_sequence_delta, cpm_ext.h) already on the device to a linear block of `bytes` bytes: one lane per payload piece
+int launch_delta_patch(cpm_ctx* ctx, const void* block_dev, uint32_t n_runs, uint64_t payload_bytes, void* voxels, uint64_t bytes, hipStream_t stream);
 
 #define CPM_HIP_CHECK(ctx, expr)                                                        \
     do {                                                                                \

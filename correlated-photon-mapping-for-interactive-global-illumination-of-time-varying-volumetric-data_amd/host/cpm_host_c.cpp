@@ -564,6 +564,20 @@ int cpmh_sequence_stream_stats(cpmh_sequence* s, double* out) {
     out[0] = (double)n; out[1] = ms; out[2] = (double)bytes; out[3] = (double)late;
     return 0;
 }
+// on != 0 (with keep_on_device 0): the player compares the elements once and uploads only what changed since the element before when that
+// element is in its ring (VolumeSequencePlayer::uploadChangesOnly, cpm_sequence_delta); off by default
+void cpmh_sequence_upload_changes_only(cpmh_sequence* s, int on) {
+    if (s) s->volumePlayer.uploadChangesOnly_.set(on != 0);
+}
+// out[0] = uploads of the changes only, out[1] = uploads in full, out[2] = PCIe bytes of the former, out[3] = host ms of the pre-pass;
+// 0 when the player uploads changes only, -1 when it does not
+int cpmh_sequence_delta_stats(cpmh_sequence* s, double* out) {
+    unsigned long long d = 0, f = 0, bytes = 0;
+    double ms = 0.0;
+    if (!s || !out || !s->volumePlayer.deltaStats(&d, &f, &bytes, &ms)) return -1;
+    out[0] = (double)d; out[1] = (double)f; out[2] = (double)bytes; out[3] = ms;
+    return 0;
+}
 void cpmh_sequence_set_time_per_element(cpmh_sequence* s, float seconds) {
     for_each_clock(s, [&](SequenceClock& c) { c.timePerElement_.set(seconds); });
 }

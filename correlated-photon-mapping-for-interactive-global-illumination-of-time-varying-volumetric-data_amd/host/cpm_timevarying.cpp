@@ -326,6 +326,7 @@ VolumeSequencePlayer::VolumeSequencePlayer() {
     addProperty(clock_.time_); addProperty(clock_.index_); addProperty(clock_.timePerElement_);
     addProperty(clock_.frameRate_); addProperty(clock_.playSequence_);
     addProperty(keepSequenceOnDevice_);
+    addProperty(uploadChangesOnly_);
     auto resize = [this]() { if (inport_.hasData()) clock_.onTimeStepChange(inport_.getData()->size()); };
     inport_.onConnect(resize);
     clock_.timePerElement_.onChange(resize);
@@ -352,7 +353,7 @@ void VolumeSequencePlayer::process() {
         // the elements stay in host memory (ref volumesequenceplayer.cpp:94-124 hands them to OpenGL, which uploads what is not resident): the two
         // this frame blends are acquired from the ring, the one after them is put on the copy stream now -- it crosses PCIe behind this frame's work
         const size_t bytes = from->getDimensions().x * from->getDimensions().y * from->getDimensions().z * from->elementSize();
-        if (stream_ && streamedSequence_ != sequence.get()) dropStream();
+        if (stream_ && (streamedSequence_ != sequence.get() || (delta_ != nullptr) != uploadChangesOnly_.get())) dropStream();
         if (!stream_) {
             cpm_volume_desc d;
             const int32_t dims[3] = { (int32_t)from->getDimensions().x, (int32_t)from->getDimensions().y, (int32_t)from->getDimensions().z };
@@ -363,6 +364,15 @@ void VolumeSequencePlayer::process() {
                 if (v->ramBytes.size() == bytes && hipHostRegister(const_cast<uint8_t*>(v->ramBytes.data()), bytes, hipHostRegisterDefault) == hipSuccess)
                     pinned_.push_back(v->ramBytes.data());
             (void)hipGetLastError();
+            if (uploadChangesOnly_.get()) {   // the pre-pass, once per sequence (the player loops: the last element's successor is the first)
+                std::vector<const void*> steps;
+                for (const auto& v : *sequence) {
+                    if (v->ramBytes.size() != bytes) { rt.check(CPM_ERR_INVALID_ARGUMENT, "VolumeSequencePlayer: an element without RAM data (or of another size) cannot be streamed"); dropStream(); return; }
+                    steps.push_back(v->ramBytes.data());
+                }
+                if (!rt.check(cpm_sequence_delta_create(rt.ctx(), &d, steps.data(), (int)steps.size(), 1, &delta_), "cpm_sequence_delta_create")) { delta_ = nullptr; dropStream(); return; }
+                if (!rt.check(cpm_volume_stream_use_delta(rt.ctx(), stream_, delta_), "cpm_volume_stream_use_delta")) { dropStream(); return; }
+            }
         }
         // (the element the walk reaches next: one further along when the clock moved on by one element since the last frame, one back when it
         // moved back by one, as before otherwise)
@@ -387,7 +397,8 @@ void VolumeSequencePlayer::process() {
 void VolumeSequencePlayer::dropStream() {
     auto& rt = CpmRuntime::get();
     if (stream_) cpm_volume_stream_destroy(rt.ctx(), stream_);   // (waits for its copy stream)
-    stream_ = nullptr; streamedSequence_ = nullptr;
+    if (delta_) cpm_sequence_delta_destroy(rt.ctx(), delta_);    // (the stream held its own reference until now)
+    stream_ = nullptr; streamedSequence_ = nullptr; delta_ = nullptr;
     for (const void* p : pinned_) (void)hipHostUnregister(const_cast<void*>(p));
     (void)hipGetLastError();
     pinned_.clear();
@@ -401,6 +412,19 @@ bool VolumeSequencePlayer::streamStats(unsigned long long* uploads, unsigned lon
     if (uploadsAtAcquire) *uploadsAtAcquire = i.uploads_at_acquire;
     if (uploadMs) *uploadMs = i.upload_ms_total;
     if (bytesPerStep) *bytesPerStep = i.bytes_per_step;
+    return true;
+}
+
+bool VolumeSequencePlayer::deltaStats(unsigned long long* deltaUploads, unsigned long long* fullUploads, unsigned long long* deltaBytes, double* analysisMs) {
+    if (!stream_ || !delta_) return false;
+    auto& rt = CpmRuntime::get();
+    cpm_volume_stream_delta_info i;
+    cpm_sequence_delta_info a;
+    if (cpm_volume_stream_delta_stats(rt.ctx(), stream_, &i) != CPM_OK || cpm_sequence_delta_get_info(rt.ctx(), delta_, &a) != CPM_OK) return false;
+    if (deltaUploads) *deltaUploads = i.delta_uploads;
+    if (fullUploads) *fullUploads = i.full_uploads;
+    if (deltaBytes) *deltaBytes = i.delta_bytes;
+    if (analysisMs) *analysisMs = a.analysis_ms;
     return true;
 }
 

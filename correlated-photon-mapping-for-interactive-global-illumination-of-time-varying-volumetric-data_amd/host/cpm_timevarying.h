@@ -112,11 +112,18 @@ public:
     // (cpm_volume_stream: the element after them is already crossing PCIe while this frame's blend, analyses and update run); for
     // sequences that do not fit on the device, and what SURVEY 8(d) counts as a time step: "upload volume, ..."
     BoolProperty keepSequenceOnDevice_{ "keepSequenceOnDevice", "Keep Sequence On Device", true };
+    // (not in the reference either) with keepSequenceOnDevice == false: the elements' RAM blocks are compared once, on first use of a sequence
+    // (cpm_sequence_delta: which 16-byte pieces change from each element to the next, the last to the first included), and an element whose
+    // predecessor is in the ring crosses PCIe as only those pieces, patched into a device copy of the predecessor
+    BoolProperty uploadChangesOnly_{ "uploadChangesOnly", "Upload Changes Only", false };
     // uploads the copy stream has carried so far / elements a frame had to wait for (not prefetched): cpmh_sequence_stream_stats
     bool streamStats(unsigned long long* uploads, unsigned long long* uploadsAtAcquire, double* uploadMs, unsigned long long* bytesPerStep);
+    // uploads of changes only / in full, PCIe bytes of the former, the pre-pass's host time: false unless uploadChangesOnly is in use
+    bool deltaStats(unsigned long long* deltaUploads, unsigned long long* fullUploads, unsigned long long* deltaBytes, double* analysisMs);
 private:
     std::shared_ptr<Volume> outVolume_;
     ::cpm_volume_stream* stream_ = nullptr;       // keepSequenceOnDevice == false
+    ::cpm_sequence_delta* delta_ = nullptr;       // ... and uploadChangesOnly: attached to stream_
     const VolumeSequence* streamedSequence_ = nullptr;
     std::vector<const void*> pinned_;             // elements' RAM blocks registered with the driver for the asynchronous copies
     size_t lastFirst_ = 0;                        // the element the last frame started from, and which way the walk has been going

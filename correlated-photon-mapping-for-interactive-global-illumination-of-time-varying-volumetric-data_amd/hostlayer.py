@@ -39,6 +39,8 @@ def load():
         "cpmh_sequence_destroy": (None, [vp]),
         "cpmh_sequence_keep_on_device": (None, [vp, i32]),
         "cpmh_sequence_stream_stats": (i32, [vp, vp]),
+        "cpmh_sequence_upload_changes_only": (None, [vp, i32]),
+        "cpmh_sequence_delta_stats": (i32, [vp, vp]),
         "cpmh_attach_sequence": (i32, [vp, vp]),
         "cpmh_sequence_step": (i32, [vp, vp, C.c_float, vp]),
         "cpmh_sequence_step_total": (i32, [vp, vp, C.c_float, vp]),
@@ -178,6 +180,18 @@ class HostSequence:
         if self.lib.cpmh_sequence_stream_stats(self.h, out) != 0:
             return None
         return {"uploads": int(out[0]), "upload_ms": float(out[1]), "bytes_per_step": int(out[2]), "uploads_at_acquire": int(out[3])}
+
+    def upload_changes_only(self, on: bool):
+        """With keep_on_device(False): compare the elements once and upload only what changed since the element before when that element is
+        in the player's ring (cpm_sequence_delta)."""
+        self.lib.cpmh_sequence_upload_changes_only(self.h, int(bool(on)))
+
+    def delta_stats(self):
+        """{"delta_uploads", "full_uploads", "delta_bytes", "analysis_ms"} of a player that uploads changes only, or None."""
+        out = (C.c_double * 4)()
+        if self.lib.cpmh_sequence_delta_stats(self.h, out) != 0:
+            return None
+        return {"delta_uploads": int(out[0]), "full_uploads": int(out[1]), "delta_bytes": int(out[2]), "analysis_ms": float(out[3])}
 
     def close(self):
         if self.h:

@@ -7,7 +7,8 @@
  *   light volume                 splat from an N * I buffer, exact incremental gather, THE FAST FORMULATION (brick bin + fixed-point
  *                                LDS-tile gather: the product's default frame), its gather into a brick-list segment
  *   correlated update            time step in one pass, occupancy bits, the fused update without a host round trip
- *   sequences                    steps streamed from pinned host memory behind the step before (cpm_volume_stream)
+ *   sequences                    steps streamed from pinned host memory behind the step before (cpm_volume_stream), or only what
+ *                                changed since the step before (cpm_sequence_delta)
  *   multi-GPU                    union-of-bricks reduce, brick lists to the display GPU, point-to-point bytes
  *   OpenGL                       buffer sharing for the light volume and the photon buffer
  */
@@ -385,6 +386,66 @@ void cpm_volume_stream_destroy(cpm_ctx* ctx, cpm_volume_stream* vs);
 int cpm_volume_stream_prefetch(cpm_ctx* ctx, cpm_volume_stream* vs, uint64_t tag, const void* host_voxels, cpm_stream consumer);
 int cpm_volume_stream_acquire(cpm_ctx* ctx, cpm_volume_stream* vs, uint64_t tag, const void* host_voxels, cpm_stream consumer, cpm_volume** out);
 int cpm_volume_stream_stats(cpm_ctx* ctx, cpm_volume_stream* vs, cpm_volume_stream_info* info);
+
+/* ---- delta uploads: a streamed step sends only the bytes that changed since the step before it ------------------------------------
+ * The reference walks the host sequence on the CPU once before any step is shown (ref dynamicvolumedifferenceanalysis.h:96-151); the
+ * same kind of pre-pass here encodes, for every transition t -> t + 1 of a host sequence, what changes, and a stream with that delta
+ * attached uploads a step as: the delta, a device copy of the step before (a slot of its ring), a patch kernel.
+ *
+ * Format.  The unit is the 16-byte PIECE of a step's flat linear block (x fastest; the last piece is short when bytes % 16 != 0).  Two
+ * steps are compared bytewise (memcmp: for f32, -0.0 against +0.0 and NaNs with different payloads are changes).  A delta is
+ *   a run table: n_runs x { uint32 first_piece, uint32 n_pieces, uint32 payload_piece_offset } -- maximal runs of changed pieces, sorted,
+ *       disjoint, payload_piece_offset the prefix sum of n_pieces (the device finds a payload piece's run by binary search, no scan);
+ *   a payload: the TARGET step's bytes of those pieces, back to back (payload_bytes = 16 x pieces, less the short piece's shortfall).
+ * What crosses PCIe for a stored transition is one block: the run table rounded up to 16 bytes, then the payload; its size is the
+ * transition's `bytes`.  A transition whose block would be larger than 3/4 of a step is not stored: it is "full" (0 runs, bytes = the
+ * step's bytes) and uploads in full.  Identical steps give 0 runs and 0 bytes.
+ *
+ * cpm_sequence_delta_encode: the encoder alone, pure host code (no context, no device).  runs_out == NULL: sizes only (*n_runs,
+ * *payload_bytes); otherwise runs_out holds 3 x *n_runs u32 (from a sizing call) and payload_out payload_capacity bytes.
+ * cpm_sequence_delta_create: the pre-pass over n_steps host steps (read during the call only), every t -> t + 1 and, with `wrap`,
+ * n_steps - 1 -> 0; the stored blocks go to pinned host memory (cpm_pinned_alloc).  At most 16 host threads.
+ * cpm_sequence_delta_transition: a forward transition's block (0 runs + the step's bytes = "full"); any other pair is refused.
+ *
+ * cpm_volume_stream_use_delta(vs, delta): attach to a stream that has uploaded nothing yet (same dims and dtype).  From then on a tag is
+ * a step index of the delta's numbering, and the host voxels handed to prefetch / acquire must be that step of the sequence the delta
+ * was made from.  When an upload of step `to` finds step `from` = to - 1 (n_steps - 1 for to = 0 with wrap) in a slot that is not the
+ * victim, and from -> to is stored, the copy stream runs: H2D of the block into the stream's staging buffer (sized at attach from the
+ * largest block; this does not wait for the consumer), the wait for the victim's consumer work, a device copy of the base slot's
+ * linear block into the victim, the patch kernel, the footprint re-layout, the `ready` event.  Every other upload is the full one:
+ * no base resident, a "full" transition, the base is the victim (a 2-slot ring walking ahead), the walk goes backwards or jumps, the
+ * first step, a tag outside the sequence.  Only forward deltas are encoded (a backward step uploads in full).  The stream holds a
+ * reference to the delta: cpm_sequence_delta_destroy may come before cpm_volume_stream_destroy.  bytes_uploaded of
+ * cpm_volume_stream_info counts delta blocks for delta uploads, upload_ms_total / uploads_timed include their H2D. */
+typedef struct cpm_sequence_delta cpm_sequence_delta;
+typedef struct cpm_sequence_delta_info {
+    int32_t n_steps;
+    int32_t n_transitions;         /* encoded: n_steps - 1, or n_steps with wrap */
+    int32_t n_delta_transitions;   /* ... of which stored as deltas (the rest are "full") */
+    int32_t wrap;
+    uint64_t step_bytes;
+    uint64_t delta_bytes_total;    /* blocks of the stored transitions */
+    uint64_t delta_bytes_max;
+    double dirty_fraction;         /* changed pieces / pieces, mean over the encoded transitions */
+    double analysis_ms;            /* host wall time of the pre-pass */
+} cpm_sequence_delta_info;
+typedef struct cpm_volume_stream_delta_info {
+    uint64_t delta_uploads;
+    uint64_t full_uploads;
+    uint64_t delta_bytes;          /* PCIe bytes of the delta uploads ... */
+    uint64_t full_bytes;           /* ... and of the full ones */
+    uint64_t delta_uploads_timed;  /* finished delta uploads whose event pair has been read ... */
+    double delta_h2d_ms_total;     /* ... and their H2D time in all */
+} cpm_volume_stream_delta_info;
+int cpm_sequence_delta_encode(const cpm_volume_desc* desc, const void* from, const void* to, uint32_t* runs_out, void* payload_out,
+                              size_t payload_capacity, uint32_t* n_runs, size_t* payload_bytes);
+int cpm_sequence_delta_create(cpm_ctx* ctx, const cpm_volume_desc* desc, const void* const* host_steps, int n_steps, int wrap,
+                              cpm_sequence_delta** out);
+int cpm_sequence_delta_get_info(cpm_ctx* ctx, const cpm_sequence_delta* delta, cpm_sequence_delta_info* info);
+int cpm_sequence_delta_transition(cpm_ctx* ctx, const cpm_sequence_delta* delta, int from, int to, uint32_t* n_runs, uint64_t* bytes);
+void cpm_sequence_delta_destroy(cpm_ctx* ctx, cpm_sequence_delta* delta);
+int cpm_volume_stream_use_delta(cpm_ctx* ctx, cpm_volume_stream* vs, cpm_sequence_delta* delta);
+int cpm_volume_stream_delta_stats(cpm_ctx* ctx, cpm_volume_stream* vs, cpm_volume_stream_delta_info* info);
 
 
 /* ------------------------------------------------------------------ multi-GPU: sparse and brick-list exchanges, point-to-point; OpenGL sharing */
