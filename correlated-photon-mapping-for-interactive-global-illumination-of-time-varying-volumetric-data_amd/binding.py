@@ -16,7 +16,7 @@ _PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = _PKG_DIR / "libcpm_hip.so"
 
 CPM_OK = 0
-CPM_U8, CPM_U16, CPM_F32 = 0, 1, 2
+CPM_U8, CPM_U16, CPM_F32, CPM_F16 = 0, 1, 2, 3
 CPM_TRACE_PROGRESSIVE = 1
 CPM_TRACE_NO_SINGLE_SCATTERING = 2
 CPM_TRACE_PHOTONS_PLANAR = 4
@@ -427,7 +427,13 @@ _TORCH_DTYPES = None
 
 def _dtype_code(t):
     import torch
-    return {torch.uint8: CPM_U8, torch.uint16: CPM_U16, torch.int16: CPM_U16, torch.float32: CPM_F32}[t.dtype]
+    return {torch.uint8: CPM_U8, torch.uint16: CPM_U16, torch.int16: CPM_U16, torch.float32: CPM_F32, torch.float16: CPM_F16}[t.dtype]
+
+
+def _np_dtype_code(dtype):
+    """cpm_dtype of a numpy voxel type (float16: IEEE binary16, CPM_F16)."""
+    import numpy as np
+    return {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32, np.dtype(np.float16): CPM_F16}[np.dtype(dtype)]
 
 
 class Context:
@@ -504,10 +510,10 @@ class Context:
 
     # -- volume / tf
     def volume_create(self, voxels, desc: VolumeDesc | None = None):
-        """voxels: torch tensor [z, y, x] (u8 / u16-as-int16|uint16 / f32) on the GPU, or a numpy array on the host."""
+        """voxels: torch tensor [z, y, x] (u8 / u16-as-int16|uint16 / f32 / f16) on the GPU, or a numpy array on the host."""
         import numpy as np
         if isinstance(voxels, np.ndarray):
-            code = {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32}[voxels.dtype]
+            code = _np_dtype_code(voxels.dtype)
             dims = voxels.shape[::-1]
             voxels = np.ascontiguousarray(voxels)
             ptr, is_dev = C.c_void_p(voxels.ctypes.data), 0
@@ -1091,7 +1097,7 @@ class Volume:
     def download(self):
         """Voxels as a numpy array [z, y, x] (blocking device -> host copy)."""
         import numpy as np
-        dt = {0: np.uint8, 1: np.uint16, 2: np.float32}[int(self.desc.dtype)]
+        dt = {CPM_U8: np.uint8, CPM_U16: np.uint16, CPM_F32: np.float32, CPM_F16: np.float16}[int(self.desc.dtype)]
         out = np.empty(tuple(self.desc.dims)[::-1], dtype=dt)
         self.ctx._check(self.ctx.lib.cpm_volume_download(self.ctx.h, self.h, C.c_void_p(out.ctypes.data), self.ctx._stream()))
         return out
@@ -1142,8 +1148,7 @@ class PinnedSequence:
 
 def _volume_desc_like(like):
     import numpy as np
-    code = {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32}[np.dtype(like.dtype)]
-    return default_volume_desc(like.shape[::-1], code)
+    return default_volume_desc(like.shape[::-1], _np_dtype_code(like.dtype))
 
 
 def sequence_delta_encode(from_arr, to_arr):
@@ -1215,8 +1220,7 @@ class VolumeStream:
         if isinstance(like, VolumeDesc):
             self.desc = like
         else:
-            code = {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32}[np.dtype(like.dtype)]
-            self.desc = default_volume_desc(like.shape[::-1], code)
+            self.desc = default_volume_desc(like.shape[::-1], _np_dtype_code(like.dtype))
         self.h = C.c_void_p()
         ctx._check(ctx.lib.cpm_volume_stream_create(ctx.h, C.byref(self.desc), n_slots, C.byref(self.h)))
 

@@ -111,7 +111,9 @@ int build_quads(cpm_ctx* ctx, cpm_volume* vol, const void* src, bool copy_linear
     vol->quads_stale = false;
     switch (vol->desc.dtype) {
         case CPM_U8: return copy_linear ? launch_quads<uint8_t, true>(ctx, vol, src, s) : launch_quads<uint8_t, false>(ctx, vol, src, s);
-        case CPM_U16: return copy_linear ? launch_quads<uint16_t, true>(ctx, vol, src, s) : launch_quads<uint16_t, false>(ctx, vol, src, s);
+        case CPM_U16:
+        case CPM_F16:  // (a bit copy: binary16 moves as its 2 bytes)
+            return copy_linear ? launch_quads<uint16_t, true>(ctx, vol, src, s) : launch_quads<uint16_t, false>(ctx, vol, src, s);
         default: return copy_linear ? launch_quads<uint32_t, true>(ctx, vol, src, s) : launch_quads<uint32_t, false>(ctx, vol, src, s);
     }
 }
@@ -288,14 +290,14 @@ float cpm_relative_irradiance_scale(double radius, double n_photons) {
     return (float)((1. / pi) / (vol * n_photons));
 }
 
-static size_t dtype_size(int dtype) { return dtype == CPM_U8 ? 1 : (dtype == CPM_U16 ? 2 : 4); }
+static size_t dtype_size(int dtype) { return dtype == CPM_U8 ? 1 : (dtype == CPM_U16 || dtype == CPM_F16 ? 2 : 4); }
 
 
 int cpm_volume_create(cpm_ctx* ctx, const cpm_volume_desc* desc, const void* voxels, int is_device,
                       cpm_stream stream, cpm_volume** out) {
     CPM_ENTER(ctx);
     CPM_REQUIRE(ctx, desc && out, "cpm_volume_create: null argument");
-    CPM_REQUIRE(ctx, desc->dtype >= CPM_U8 && desc->dtype <= CPM_F32, "cpm_volume_create: dtype");
+    CPM_REQUIRE(ctx, desc->dtype >= CPM_U8 && desc->dtype <= CPM_F16, "cpm_volume_create: dtype");
     CPM_REQUIRE(ctx, desc->dims[0] >= 2 && desc->dims[1] >= 1 && desc->dims[2] >= 1, "cpm_volume_create: dims (x >= 2)");
     Affine a;
     if (!affine_from_matrix(desc->texture_to_index, a) || !affine_from_matrix(desc->index_to_texture, a))

@@ -48,6 +48,7 @@ struct BrickVol {
 CPM_DEV float raw_voxel(const void* v, int dtype, size_t idx) {
     if (dtype == CPM_U8) return (float)static_cast<const uint8_t*>(v)[idx];
     if (dtype == CPM_U16) return (float)static_cast<const uint16_t*>(v)[idx];
+    if (dtype == CPM_F16) return half_to_float(static_cast<const uint16_t*>(v)[idx]);
     return static_cast<const float*>(v)[idx];
 }
 
@@ -84,7 +85,8 @@ __global__ __launch_bounds__(64) void minmax_kernel(BrickVol V, uint16_t* __rest
 
 // VolumeRAMDifferenceAnalysisDispatcher (ref uniformgridcl/processors/dynamicvolumedifferenceanalysis.h:96-151):
 // mean |b - a| per brick over the format's range; integer formats sum exactly (u64),
-// float volumes are summed by one lane in the reference's x-y-z order (double).
+// float volumes are summed by one lane in the reference's x-y-z order (double) -- binary16 ones over their widened values, so
+// that they give the F32 volume's bits.
 __global__ __launch_bounds__(64) void difference_kernel(BrickVol A, const void* __restrict__ bvox, double range,
                                                         float* __restrict__ out) {
     const int brick = blockIdx.x;
@@ -92,14 +94,14 @@ __global__ __launch_bounds__(64) void difference_kernel(BrickVol A, const void* 
     const int x0 = gx * A.region, y0 = gy * A.region, z0 = gz * A.region;
     const int ex = min(x0 + A.region, A.dx), ey = min(y0 + A.region, A.dy), ez = min(z0 + A.region, A.dz);
     const double cnt = (double)A.region * A.region * A.region;
-    if (A.dtype == CPM_F32) {
+    if (A.dtype == CPM_F32 || A.dtype == CPM_F16) {
         if (threadIdx.x != 0) return;
         double sum = 0;
         for (int z = z0; z < ez; ++z)
             for (int y = y0; y < ey; ++y)
                 for (int x = x0; x < ex; ++x) {
                     size_t i = (size_t)x + (size_t)A.dx * ((size_t)y + (size_t)A.dy * (size_t)z);
-                    sum += fabs((double)static_cast<const float*>(bvox)[i] - (double)static_cast<const float*>(A.voxels)[i]);
+                    sum += fabs((double)raw_voxel(bvox, A.dtype, i) - (double)raw_voxel(A.voxels, A.dtype, i));
                 }
         out[brick] = (float)((sum / cnt) / range);
         return;
@@ -135,6 +137,23 @@ CPM_DEV uint32_t float_key(float f) {  // order-preserving float -> uint
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 CPM_DEV float key_float(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// binary16 (low 16 bits): the same order-preserving key in 16 bits, and its inverse.  NaNs get no key (the min / max skip them, as
+// minmax_kernel's fminf / fmaxf do on the widened values).
+CPM_DEV bool half_is_nan(uint32_t h) { return (h & 0x7fffu) > 0x7c00u; }
+CPM_DEV uint32_t half_key(uint32_t h) { return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u); }
+CPM_DEV float key_half(uint32_t k) { return half_to_float((k & 0x8000u) ? (k & 0x7fffu) : (~k & 0xffffu)); }
+// a finite binary16 times 2^24, exactly: every finite binary16 is a multiple of 2^-24 below 2^16, so |b - a| * 2^24 is an integer
+// below 2^41 and a brick of up to 16^3 such terms sums below 2^53 -- where the F32 path's double sum is exact in any order too
+CPM_DEV long long half_fixed24(uint32_t h) {
+    const uint32_t e = (h >> 10) & 31u, m = h & 1023u;
+    const long long mag = e ? (long long)(m | 1024u) << (e - 1) : (long long)m;
+    return (h & 0x8000u) ? -mag : mag;
+}
+// binary16 difference bricks: a term with a NaN operand, or inf - inf, is NaN; any other with an inf operand is inf.  The per-brick
+// flags sit above the sum's 53 bits of the same LDS slot (ds_or_b64); the sequential double sum of non-negative terms is NaN if a term
+// is, else inf if a term is, which the flags reproduce.
+constexpr unsigned long long kHalfNanTerm = 1ull << 62, kHalfInfTerm = 1ull << 61, kHalfSumMask = (1ull << 61) - 1;
+constexpr int kHalfMaxStreamRegion = 16;
 
 // MODE 0: min / max bricks of A; 1: mean |B - A| bricks; 2: both in one pass -- the difference against A and the min / max
 // of B (a time step: the new volume's bricks and what changed, with each volume read once)
@@ -145,7 +164,7 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
     extern __shared__ unsigned long long s_slots[];  // DIFF: ox sums; MINMAX: ox minima and ox maxima (u32) behind them
     uint32_t* s_min = reinterpret_cast<uint32_t*>(s_slots + (DIFF ? A.ox : 0));
     uint32_t* s_max = s_min + A.ox;
-    constexpr int ES = DT == CPM_U8 ? 1 : (DT == CPM_U16 ? 2 : 4);
+    constexpr int ES = DT == CPM_U8 ? 1 : (DT == CPM_U16 || DT == CPM_F16 ? 2 : 4);
     constexpr int EPC = 16 / ES;  // elements per 16-byte chunk
     const int gy = blockIdx.x % A.oy, gz = blockIdx.x / A.oy;
     const int R = A.region;
@@ -170,27 +189,43 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
         const int xb = xc * EPC;
         int g = xb / R, left = R - (xb - g * R);  // brick of the first element, elements left in it
         uint32_t mn = 0xffffffffu, mx = 0u;
-        unsigned long long sum = 0;
+        unsigned long long sum = 0, flags = 0;  // (flags: F16's non-finite difference terms)
         bool any = false;
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             if (xb + e < A.dx) {
                 uint32_t va, vb = 0;
                 if (DT == CPM_U8) { va = (wa[e >> 2] >> (8 * (e & 3))) & 0xffu; vb = (wb[e >> 2] >> (8 * (e & 3))) & 0xffu; }
-                else if (DT == CPM_U16) { va = (wa[e >> 1] >> (16 * (e & 1))) & 0xffffu; vb = (wb[e >> 1] >> (16 * (e & 1))) & 0xffffu; }
+                else if (DT == CPM_U16 || DT == CPM_F16) { va = (wa[e >> 1] >> (16 * (e & 1))) & 0xffffu; vb = (wb[e >> 1] >> (16 * (e & 1))) & 0xffffu; }
                 else va = float_key(__uint_as_float(wa[e]));
-                if (DIFF) sum += va > vb ? va - vb : vb - va;
-                if (MINMAX) { const uint32_t vm = MODE == 2 ? vb : va; mn = vm < mn ? vm : mn; mx = vm > mx ? vm : mx; }
+                if (DT == CPM_F16) {
+                    if (DIFF) {
+                        const bool fa = (va & 0x7c00u) != 0x7c00u, fb = (vb & 0x7c00u) != 0x7c00u;
+                        if (fa && fb) {
+                            const long long d = half_fixed24(vb) - half_fixed24(va);
+                            sum += (unsigned long long)(d < 0 ? -d : d);
+                        } else {
+                            flags |= half_is_nan(va) || half_is_nan(vb) || (!fa && !fb && ((va ^ vb) & 0x8000u) == 0) ? kHalfNanTerm : kHalfInfTerm;
+                        }
+                    }
+                    if (MINMAX) {
+                        const uint32_t vm = MODE == 2 ? vb : va;
+                        if (!half_is_nan(vm)) { const uint32_t k = half_key(vm); mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
+                    }
+                } else {
+                    if (DIFF) sum += va > vb ? va - vb : vb - va;
+                    if (MINMAX) { const uint32_t vm = MODE == 2 ? vb : va; mn = vm < mn ? vm : mn; mx = vm > mx ? vm : mx; }
+                }
                 any = true;
                 if (--left == 0) {  // the brick ends inside the chunk
-                    if (DIFF) atomicAdd(&s_slots[g], sum);
+                    if (DIFF) { atomicAdd(&s_slots[g], sum); if (DT == CPM_F16 && flags) atomicOr(&s_slots[g], flags); }
                     if (MINMAX) { atomicMin(&s_min[g], mn); atomicMax(&s_max[g], mx); }
-                    ++g; left = R; mn = 0xffffffffu; mx = 0u; sum = 0; any = false;
+                    ++g; left = R; mn = 0xffffffffu; mx = 0u; sum = 0; flags = 0; any = false;
                 }
             }
         }
         if (any) {
-            if (DIFF) atomicAdd(&s_slots[g], sum);
+            if (DIFF) { atomicAdd(&s_slots[g], sum); if (DT == CPM_F16 && flags) atomicOr(&s_slots[g], flags); }
             if (MINMAX) { atomicMin(&s_min[g], mn); atomicMax(&s_max[g], mx); }
         }
     }
@@ -199,14 +234,22 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
         const size_t brick = (size_t)g + (size_t)A.ox * ((size_t)gy + (size_t)A.oy * (size_t)gz);
         if (DIFF) {
             const double cnt = (double)R * R * R;
-            diff_out[brick] = (float)(((double)s_slots[g] / cnt) / range);
+            if (DT == CPM_F16) {
+                const unsigned long long v = s_slots[g];
+                const double sum = (v & kHalfNanTerm) ? (double)__builtin_nanf("") : (v & kHalfInfTerm) ? (double)__builtin_inff()
+                                                                                                       : (double)(v & kHalfSumMask) * 0x1p-24;
+                diff_out[brick] = (float)((sum / cnt) / range);
+            } else {
+                diff_out[brick] = (float)(((double)s_slots[g] / cnt) / range);
+            }
         }
         if (MINMAX) {
-            const float lo = DT == CPM_F32 ? key_float(s_min[g]) : (float)s_min[g];
-            const float hi = DT == CPM_F32 ? key_float(s_max[g]) : (float)s_max[g];
+            const float lo = DT == CPM_F32 ? key_float(s_min[g]) : DT == CPM_F16 ? key_half(s_min[g]) : (float)s_min[g];
+            const float hi = DT == CPM_F32 ? key_float(s_max[g]) : DT == CPM_F16 ? key_half(s_max[g]) : (float)s_max[g];
             const float a = (lo * A.norm + A.offset) * A.one_minus_scaling;
             const float b = (hi * A.norm + A.offset) * A.one_minus_scaling;
-            const float mnv = min_(kFltMax, min_(a, b)), mxv = max_(0.f, max_(a, b));  // the reference's initial values
+            float mnv = min_(kFltMax, min_(a, b)), mxv = max_(0.f, max_(a, b));  // the reference's initial values
+            if (DT == CPM_F16 && s_min[g] == 0xffffffffu) { mnv = kFltMax; mxv = 0.f; }  // NaNs only: nothing taken, as in minmax_kernel
             mm_out[2 * brick] = (uint16_t)__builtin_rintf(min_(max_(mnv, 0.f), 1.f) * 65535.f);
             mm_out[2 * brick + 1] = (uint16_t)__builtin_rintf(min_(max_(mxv, 0.f), 1.f) * 65535.f);
         }
@@ -215,7 +258,7 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
 
 // rows must start on 16-byte boundaries for the vector loads (hipMalloc aligns the block itself)
 bool rows_are_16_byte_aligned(const BrickVol& V) {
-    const int es = V.dtype == CPM_U8 ? 1 : (V.dtype == CPM_U16 ? 2 : 4);
+    const int es = V.dtype == CPM_U8 ? 1 : (V.dtype == CPM_U16 || V.dtype == CPM_F16 ? 2 : 4);
     return ((size_t)V.dx * es) % 16 == 0;
 }
 
@@ -856,6 +899,7 @@ int cpm_volume_minmax(cpm_ctx* ctx, const cpm_volume* vol, int region, uint16_t*
         switch (V.dtype) {
             case CPM_U8: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U8, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
             case CPM_U16: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U16, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
+            case CPM_F16: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F16, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
             default: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F32, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
         }
         CPM_LAUNCH_CHECK(ctx, "brick_row_kernel");
@@ -876,12 +920,15 @@ int cpm_volume_difference(cpm_ctx* ctx, const cpm_volume* cur, const cpm_volume*
     CPM_REQUIRE(ctx, memcmp(cur->desc.dims, next->desc.dims, sizeof(cur->desc.dims)) == 0 && cur->desc.dtype == next->desc.dtype,
                 "cpm_volume_difference: volumes differ in shape or type");
     double range = V.dtype == CPM_U8 ? 255.0 : (V.dtype == CPM_U16 ? 65535.0 : 1.0);
-    if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && rows_are_16_byte_aligned(V) && (size_t)V.ox * 8 <= 48 * 1024) {
-        // (float volumes keep the per-brick kernel: their sum is defined in the reference's x-y-z order in double)
+    if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && (V.dtype != CPM_F16 || region <= kHalfMaxStreamRegion) &&
+        rows_are_16_byte_aligned(V) && (size_t)V.ox * 8 <= 48 * 1024) {
+        // (f32 volumes keep the per-brick kernel: their sum is defined in the reference's x-y-z order in double; f16 ones take
+        // the streaming kernel only where that double sum is exact -- region <= 16 -- and so order-free)
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
         const size_t lds = (size_t)V.ox * 8;
         hipStream_t s = (hipStream_t)stream;
         if (V.dtype == CPM_U8) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U8, 1>), grid, block, lds, s, V, next->voxels, range, nullptr, out);
+        else if (V.dtype == CPM_F16) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F16, 1>), grid, block, lds, s, V, next->voxels, range, nullptr, out);
         else CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U16, 1>), grid, block, lds, s, V, next->voxels, range, nullptr, out);
         CPM_LAUNCH_CHECK(ctx, "brick_row_kernel");
         return CPM_OK;
@@ -900,13 +947,15 @@ int cpm_volume_step(cpm_ctx* ctx, const cpm_volume* cur, const cpm_volume* next,
     CPM_REQUIRE(ctx, next && mean_abs_diff && next_minmax2, "cpm_volume_step: null argument");
     CPM_REQUIRE(ctx, memcmp(cur->desc.dims, next->desc.dims, sizeof(cur->desc.dims)) == 0 && cur->desc.dtype == next->desc.dtype,
                 "cpm_volume_step: volumes differ in shape or type");
-    if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && rows_are_16_byte_aligned(V) && (size_t)V.ox * 16 <= 48 * 1024 &&
+    if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && (V.dtype != CPM_F16 || region <= kHalfMaxStreamRegion) &&
+        rows_are_16_byte_aligned(V) && (size_t)V.ox * 16 <= 48 * 1024 &&
         cur->desc.format_offset == next->desc.format_offset && cur->desc.format_scaling == next->desc.format_scaling) {
-        const double range = V.dtype == CPM_U8 ? 255.0 : 65535.0;
+        const double range = V.dtype == CPM_U8 ? 255.0 : (V.dtype == CPM_U16 ? 65535.0 : 1.0);
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
         const size_t lds = (size_t)V.ox * 16;
         hipStream_t s = (hipStream_t)stream;
         if (V.dtype == CPM_U8) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U8, 2>), grid, block, lds, s, V, next->voxels, range, next_minmax2, mean_abs_diff);
+        else if (V.dtype == CPM_F16) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F16, 2>), grid, block, lds, s, V, next->voxels, range, next_minmax2, mean_abs_diff);
         else CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U16, 2>), grid, block, lds, s, V, next->voxels, range, next_minmax2, mean_abs_diff);
         CPM_LAUNCH_CHECK(ctx, "brick_row_kernel");
         return CPM_OK;
@@ -1416,6 +1465,7 @@ int retrace_impl(cpm_ctx* ctx, cpm_selection* s, const float* importance_grid, c
     switch (vol->desc.dtype) {
         case CPM_U8: CPM_RETRACE_LAUNCH(CPM_U8); break;
         case CPM_U16: CPM_RETRACE_LAUNCH(CPM_U16); break;
+        case CPM_F16: CPM_RETRACE_LAUNCH(CPM_F16); break;
         default: CPM_RETRACE_LAUNCH(CPM_F32); break;
     }
 #undef CPM_RETRACE_LAUNCH_L

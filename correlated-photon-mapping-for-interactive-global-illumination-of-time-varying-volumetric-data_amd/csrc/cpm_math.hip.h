@@ -26,6 +26,9 @@ CPM_DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); 
 CPM_DEV float min_(float a, float b) { return __builtin_fminf(a, b); }
 CPM_DEV float max_(float a, float b) { return __builtin_fmaxf(a, b); }
 CPM_DEV float lerp_(float x, float y, float a) { return fma_(a, y, fma_(-a, x, x)); }
+// CPM_F16 voxels: the exact widening of an IEEE binary16 (the low 16 bits of h) to binary32 -- one v_cvt_f32_f16 (subnormals
+// included: every binary16 is a normal or zero binary32)
+CPM_DEV float half_to_float(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }
 
 // natural log, x in [0, inf) normal; log(0) = -inf
 CPM_DEV float log_(float x) {

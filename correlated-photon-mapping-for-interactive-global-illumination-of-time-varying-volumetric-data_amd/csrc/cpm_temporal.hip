@@ -83,6 +83,14 @@ CPM_DEV uint32_t mix_u8_word(const float* lut, uint32_t x, uint32_t y, float a, 
 CPM_DEV uint32_t mix_u16_word(uint32_t x, uint32_t y, float a, float oma) {
     return mix_unorm<16>(x & 0xffffu, y & 0xffffu, a, oma) | (mix_unorm<16>(x >> 16, y >> 16, a, oma) << 16);
 }
+// binary16: both texels widened, the f32 branch's mix, rounded to nearest even (v_cvt_f16_f32) -- the F32 result of the widened
+// volumes, narrowed
+CPM_DEV uint32_t mix_f16_half(uint32_t x, uint32_t y, float a, float oma) {
+    return __builtin_bit_cast(uint16_t, (_Float16)mix_glsl(half_to_float(x), half_to_float(y), a, oma));
+}
+CPM_DEV uint32_t mix_f16_word(uint32_t x, uint32_t y, float a, float oma) {
+    return mix_f16_half(x, y, a, oma) | (mix_f16_half(x >> 16, y >> 16, a, oma) << 16);
+}
 
 // volumes are allocated with a 16-byte tail pad (cpm_volume_create), so whole uint4 words cover them
 template <int DT>
@@ -103,6 +111,9 @@ __global__ __launch_bounds__(256) void volume_mix_kernel(const uint4* __restrict
         } else if (DT == CPM_U16) {
             r = make_uint4(mix_u16_word(p.x, q.x, a, oma), mix_u16_word(p.y, q.y, a, oma), mix_u16_word(p.z, q.z, a, oma),
                            mix_u16_word(p.w, q.w, a, oma));
+        } else if (DT == CPM_F16) {
+            r = make_uint4(mix_f16_word(p.x, q.x, a, oma), mix_f16_word(p.y, q.y, a, oma), mix_f16_word(p.z, q.z, a, oma),
+                           mix_f16_word(p.w, q.w, a, oma));
         } else {
             r = make_uint4(__float_as_uint(mix_glsl(__uint_as_float(p.x), __uint_as_float(q.x), a, oma)),
                            __float_as_uint(mix_glsl(__uint_as_float(p.y), __uint_as_float(q.y), a, oma)),
@@ -168,6 +179,7 @@ int cpm_volume_mix(cpm_ctx* ctx, const cpm_volume* v0, const cpm_volume* v1, flo
     switch (v0->desc.dtype) {
         case CPM_U8: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_U8>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
         case CPM_U16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_U16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
+        case CPM_F16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_F16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
         default: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_F32>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
     }
     CPM_LAUNCH_CHECK(ctx, "volume_mix_kernel");

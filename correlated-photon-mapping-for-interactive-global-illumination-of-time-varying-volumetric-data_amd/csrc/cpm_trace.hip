@@ -221,7 +221,7 @@ int make_trace_args(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const
     A.vol.sy = (uint32_t)d.dims[0];
     A.vol.sz = (uint32_t)d.dims[0] * (uint32_t)d.dims[1];
     A.vol.mul24 = A.vol.sz < (1u << 24) && d.dims[0] < (1 << 24) && d.dims[1] < (1 << 24) && d.dims[2] < (1 << 24);
-    A.vol.norm = d.dtype == CPM_U8 ? (1.0f / 255.0f) : (d.dtype == CPM_U16 ? (1.0f / 65535.0f) : 1.0f);
+    A.vol.norm = d.dtype == CPM_U8 ? (1.0f / 255.0f) : (d.dtype == CPM_U16 ? (1.0f / 65535.0f) : 1.0f);  // (F16, F32: 1)
     A.vol.offset = d.format_offset;
     A.vol.one_minus_scaling = 1.0f - d.format_scaling;
     A.tf_alpha = tf->alpha;
@@ -407,12 +407,14 @@ int trace_impl(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const cpm_
         switch (d.dtype) {
             case CPM_U8: CPM_TRACE_LAUNCH_MULTI(CPM_U8); break;
             case CPM_U16: CPM_TRACE_LAUNCH_MULTI(CPM_U16); break;
+            case CPM_F16: CPM_TRACE_LAUNCH_MULTI(CPM_F16); break;
             default: CPM_TRACE_LAUNCH_MULTI(CPM_F32); break;
         }
     } else
     switch (d.dtype) {
         case CPM_U8: CPM_TRACE_LAUNCH(CPM_U8); break;
         case CPM_U16: CPM_TRACE_LAUNCH(CPM_U16); break;
+        case CPM_F16: CPM_TRACE_LAUNCH(CPM_F16); break;
         default: CPM_TRACE_LAUNCH(CPM_F32); break;
     }
 #undef CPM_TRACE_LAUNCH_MULTI

@@ -89,6 +89,19 @@ template <> struct FootprintLoad<CPM_U16> {
         }
     }
 };
+// binary16: the 2-byte footprint of u16, each texel widened on its own (v_cvt_f32_f16, the high halves through op_sel / SDWA) before
+// the f32 path's lerps -- no packed-f16 arithmetic, so a sample is the bits of the F32 volume of the widened values
+template <> struct FootprintLoad<CPM_F16> {
+    static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
+        uint32_t w[4];
+        __builtin_memcpy(w, static_cast<const uint16_t*>(base) + 4 * (size_t)idx, 16);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i + 0] = half_to_float(w[i]);
+            v[2 * i + 1] = half_to_float(w[i] >> 16);
+        }
+    }
+};
 template <> struct FootprintLoad<CPM_F32> {
     static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
         __builtin_memcpy(v, static_cast<const float*>(base) + 4 * (size_t)idx, 32);
@@ -107,7 +120,9 @@ CPM_DEV void coord(float s, float dimf, float m1, float m2, float& fl, float& a)
 // The same eight voxels from the volume's linear block (x fastest): four fetches of an x-pair, rows (y, z), (y', z), (y, z'), (y', z')
 // with y' = min(y + 1, dim.y - 1), z' likewise -- exactly what a footprint element holds -- into the same order.
 template <int DT> struct LinearLoad {
-    typedef typename std::conditional<DT == CPM_U8, uint8_t, typename std::conditional<DT == CPM_U16, uint16_t, float>::type>::type T;
+    typedef typename std::conditional<DT == CPM_U8, uint8_t,
+            typename std::conditional<DT == CPM_U16 || DT == CPM_F16, uint16_t, float>::type>::type T;
+    static CPM_DEV float widen(T t) { return DT == CPM_F16 ? half_to_float(t) : (float)t; }
     static CPM_DEV void load(const VolDev& V, uint32_t b00, int iy, int iz, float (&v)[8]) {
         const T* base = static_cast<const T*>(V.voxels) + b00;
         const uint32_t up = (float)iy < V.my1 ? V.sy : 0u, back = (float)iz < V.mz1 ? V.sz : 0u;
@@ -116,7 +131,7 @@ template <int DT> struct LinearLoad {
         for (int k = 0; k < 4; ++k) {
             T pr[2];
             __builtin_memcpy(pr, base + off[k], sizeof(pr));
-            v[k] = (float)pr[0]; v[4 + k] = (float)pr[1];
+            v[k] = widen(pr[0]); v[4 + k] = widen(pr[1]);
         }
     }
 };

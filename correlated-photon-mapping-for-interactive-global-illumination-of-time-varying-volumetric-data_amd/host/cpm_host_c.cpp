@@ -379,6 +379,10 @@ int cpmh_sequence_set_time(cpmh_sequence* s, float time);
 static std::string g_u3d_error;
 const char* cpmh_last_error() { return g_u3d_error.c_str(); }
 
+// the host Volume's view of a cpm_dtype: bytes per voxel and getDataFormat()->getString() (no device needed)
+int cpmh_volume_element_size(int dtype) { return (int)Volume(size3_t{ 1, 1, 1 }, dtype).elementSize(); }
+const char* cpmh_volume_format(int dtype) { return Volume(size3_t{ 1, 1, 1 }, dtype).getDataFormatString(); }
+
 static std::shared_ptr<UniformGrid3DBase> make_grid(int format) {
     if (format == 0) return std::make_shared<MinMaxUniformGrid3D>();
     return std::make_shared<ImportanceUniformGrid3D>();

@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include "cpm/cpm.h"  // cpm_dtype
+
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -133,7 +135,11 @@ public:
     size3_t getDimensions() const { return dims_; }
     void setDimensions(size3_t d) { dims_ = d; data.setSize(0); invalidateDeviceRepresentation(); }
     int dtype() const { return dtype_; }
-    size_t elementSize() const { return dtype_ == 0 ? 1 : (dtype_ == 1 ? 2 : 4); }
+    size_t elementSize() const { return dtype_ == CPM_U8 ? 1 : (dtype_ == CPM_U16 || dtype_ == CPM_F16 ? 2 : 4); }
+    // getDataFormat()->getString() of the scalar formats the path takes (cpm_dtype)
+    const char* getDataFormatString() const {
+        return dtype_ == CPM_U8 ? "UINT8" : dtype_ == CPM_U16 ? "UINT16" : dtype_ == CPM_F16 ? "FLOAT16" : "FLOAT32";
+    }
     const mat4& getModelMatrix() const { return model_; }
     const mat4& getWorldMatrix() const { return world_; }
     void setModelMatrix(const mat4& m) { model_ = m; }

@@ -53,14 +53,14 @@ def load():
 
 class HostNetwork:
     """The CorrelatedPhotonMappingSingleVolume network in C++ (sample generator -> light sampler -> tracer -> light volume,
-    min/max -> importance -> tracer): cpmh_create's wiring."""
+    min/max -> importance -> tracer): cpmh_create's wiring.  The volume's numpy type picks the format (uint8, uint16, float32, float16)."""
 
     def __init__(self, lib, volume_u8, n_side, light_position, light_direction, tf_points, size_option=2, max_scattering=1,
                  correlated=True):
         self.lib = lib
         vol = np.ascontiguousarray(volume_u8)
         pts = np.ascontiguousarray(np.asarray(tf_points, np.float32))
-        self.h = lib.cpmh_create(vol.ctypes.data, 0, vol.shape[2], vol.shape[1], vol.shape[0], n_side, n_side,
+        self.h = lib.cpmh_create(vol.ctypes.data, B._np_dtype_code(vol.dtype), vol.shape[2], vol.shape[1], vol.shape[0], n_side, n_side,
                                  C.byref((C.c_float * 3)(*light_position)), C.byref((C.c_float * 3)(*light_direction)),
                                  pts.ctypes.data, pts.shape[0], size_option, max_scattering, int(correlated))
         if not self.h:
@@ -147,7 +147,7 @@ class HostSequence:
     def __init__(self, lib, volumes_u8, region=8):
         self.lib = lib
         v = np.ascontiguousarray(volumes_u8)
-        self.h = lib.cpmh_sequence_create(v.ctypes.data, 0, v.shape[3], v.shape[2], v.shape[1], v.shape[0], region)
+        self.h = lib.cpmh_sequence_create(v.ctypes.data, B._np_dtype_code(v.dtype), v.shape[3], v.shape[2], v.shape[1], v.shape[0], region)
         if not self.h:
             raise RuntimeError("cpmh_sequence_create failed")
 

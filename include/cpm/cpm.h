@@ -102,7 +102,14 @@ int cpm_random_fill(cpm_ctx* ctx, uint32_t* state, size_t n, int draws, float* o
 
 /* ------------------------------------------------------------------ volume / TF */
 
-typedef enum cpm_dtype { CPM_U8 = 0, CPM_U16 = 1, CPM_F32 = 2 } cpm_dtype;
+/* CPM_F16: IEEE binary16 voxels, x fastest.  A voxel's value is its exact widening to f32, mapped like an f32 voxel
+ * ((v + format_offset) * (1 - format_scaling), norm 1); the tracer widens the 8 texels of a trilinear sample first and
+ * interpolates with the f32 path's lerps (an OpenCL CL_HALF_FLOAT image under linear filtering).  Invariant: every operation on
+ * an F16 volume gives the bits the same operation gives on the F32 volume holding the widened values -- photons, RNG state,
+ * min/max and difference bricks, importance, selections, light volumes; where the result is itself a volume (cpm_volume_mix)
+ * it is the f32 result rounded to nearest even.  (Min/max bricks: NaN voxels are ignored, as the per-brick f32 form ignores
+ * them; difference bricks: a NaN term makes the brick NaN, else an inf term makes it inf -- the f32 path's double sum.) */
+typedef enum cpm_dtype { CPM_U8 = 0, CPM_U16 = 1, CPM_F32 = 2, CPM_F16 = 3 } cpm_dtype;
 
 /* Mirrors the fields of Inviwo's VolumeParameters the path reads
  * (ref use sites progressivephotonmapping/cl/photontracer.cl:75,
