@@ -137,8 +137,11 @@ CPM_DEV uint32_t float_key(float f) {  // order-preserving float -> uint
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 CPM_DEV float key_float(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-// binary16 (low 16 bits): the same order-preserving key in 16 bits, and its inverse.  NaNs get no key (the min / max skip them, as
-// minmax_kernel's fminf / fmaxf do on the widened values).
+// A float voxel that minmax_kernel's fminf / fmaxf pass over: its mapped value is NaN -- a NaN voxel, or an infinite one where
+// format_scaling == 1 (inf * 0).  The float volumes' keys skip it; the voxels left map monotonically to numbers, so their raw extremes
+// still give the brick's mapped extremes, and a brick with none left keeps the initial (FLT_MAX, 0).
+CPM_DEV bool maps_to_nan(float v, const BrickVol& A) { return __builtin_isnan((v * A.norm + A.offset) * A.one_minus_scaling); }
+// binary16 (low 16 bits): the same order-preserving key in 16 bits, and its inverse.
 CPM_DEV bool half_is_nan(uint32_t h) { return (h & 0x7fffu) > 0x7c00u; }
 CPM_DEV uint32_t half_key(uint32_t h) { return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u); }
 CPM_DEV float key_half(uint32_t k) { return half_to_float((k & 0x8000u) ? (k & 0x7fffu) : (~k & 0xffffu)); }
@@ -160,6 +163,7 @@ constexpr int kHalfMaxStreamRegion = 16;
 template <int DT, int MODE>
 __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* __restrict__ bvox, double range,
                                                         uint16_t* __restrict__ mm_out, float* __restrict__ diff_out) {
+    static_assert(DT != CPM_F32 || MODE == 0, "an F32 voxel's va is an order key, not a value: no difference terms from it");
     constexpr bool DIFF = MODE != 0, MINMAX = MODE != 1;
     extern __shared__ unsigned long long s_slots[];  // DIFF: ox sums; MINMAX: ox minima and ox maxima (u32) behind them
     uint32_t* s_min = reinterpret_cast<uint32_t*>(s_slots + (DIFF ? A.ox : 0));
@@ -197,8 +201,10 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
                 uint32_t va, vb = 0;
                 if (DT == CPM_U8) { va = (wa[e >> 2] >> (8 * (e & 3))) & 0xffu; vb = (wb[e >> 2] >> (8 * (e & 3))) & 0xffu; }
                 else if (DT == CPM_U16 || DT == CPM_F16) { va = (wa[e >> 1] >> (16 * (e & 1))) & 0xffffu; vb = (wb[e >> 1] >> (16 * (e & 1))) & 0xffffu; }
-                else va = float_key(__uint_as_float(wa[e]));
-                if (DT == CPM_F16) {
+                else va = wa[e];
+                if (DT == CPM_F32) {  // (MODE 0)
+                    if (!maps_to_nan(__uint_as_float(va), A)) { const uint32_t k = float_key(__uint_as_float(va)); mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
+                } else if (DT == CPM_F16) {
                     if (DIFF) {
                         const bool fa = (va & 0x7c00u) != 0x7c00u, fb = (vb & 0x7c00u) != 0x7c00u;
                         if (fa && fb) {
@@ -210,7 +216,7 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
                     }
                     if (MINMAX) {
                         const uint32_t vm = MODE == 2 ? vb : va;
-                        if (!half_is_nan(vm)) { const uint32_t k = half_key(vm); mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
+                        if (!maps_to_nan(half_to_float(vm), A)) { const uint32_t k = half_key(vm); mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
                     }
                 } else {
                     if (DIFF) sum += va > vb ? va - vb : vb - va;
@@ -249,7 +255,7 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
             const float a = (lo * A.norm + A.offset) * A.one_minus_scaling;
             const float b = (hi * A.norm + A.offset) * A.one_minus_scaling;
             float mnv = min_(kFltMax, min_(a, b)), mxv = max_(0.f, max_(a, b));  // the reference's initial values
-            if (DT == CPM_F16 && s_min[g] == 0xffffffffu) { mnv = kFltMax; mxv = 0.f; }  // NaNs only: nothing taken, as in minmax_kernel
+            if ((DT == CPM_F32 || DT == CPM_F16) && s_min[g] == 0xffffffffu) { mnv = kFltMax; mxv = 0.f; }  // nothing taken, as in minmax_kernel
             mm_out[2 * brick] = (uint16_t)__builtin_rintf(min_(max_(mnv, 0.f), 1.f) * 65535.f);
             mm_out[2 * brick + 1] = (uint16_t)__builtin_rintf(min_(max_(mxv, 0.f), 1.f) * 65535.f);
         }
