@@ -45,6 +45,7 @@ EXT_SYMBOLS = [
     "cpm_volume_step", "cpm_importance_tf_occupancy", "cpm_selection_create", "cpm_selection_destroy", "cpm_selection_begin",
     "cpm_photon_importance_select", "cpm_photon_importance_retrace", "cpm_photon_importance_retrace_lights", "cpm_photon_importance_equal_select",
     "cpm_selection_finish", "cpm_selection_set_occupancy", "cpm_selection_count_device", "cpm_selection_count", "cpm_trace_selected", "cpm_splat_delta",
+    "cpm_update_budget", "cpm_selection_select_pending", "cpm_selection_finish_budget", "cpm_selection_counts",
     "cpm_pinned_alloc", "cpm_pinned_free", "cpm_volume_stream_create", "cpm_volume_stream_destroy", "cpm_volume_stream_prefetch",
     "cpm_volume_stream_acquire", "cpm_volume_stream_stats", "cpm_sequence_delta_encode", "cpm_sequence_delta_create",
     "cpm_sequence_delta_get_info", "cpm_sequence_delta_transition", "cpm_sequence_delta_destroy", "cpm_volume_stream_use_delta",
@@ -333,6 +334,10 @@ def load_library() -> C.CDLL:
         "cpm_selection_finish": (i32, [vp, vp, vp, vp]),
         "cpm_selection_count_device": (vp, [vp]),
         "cpm_selection_count": (i32, [vp, vp, P(i32)]),
+        "cpm_update_budget": (i32, [sz, C.c_float]),
+        "cpm_selection_select_pending": (i32, [vp, vp, vp, i32, i32, vp]),
+        "cpm_selection_finish_budget": (i32, [vp, vp, vp, i32, vp, vp]),
+        "cpm_selection_counts": (i32, [vp, vp, P(i32), P(i32)]),
         "cpm_trace_selected": (i32, [vp, vp, vp, vp, P(f32 * 8), P(TraceParams), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "cpm_splat_delta": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, P(GridDesc), f32, f32, i32, i32, vp, vp, vp]),
         "cpm_mix_buffers": (i32, [vp, vp, vp, f32, sz, i32, vp, vp]),
@@ -932,6 +937,10 @@ class Context:
         self._check(self.lib.cpm_select_recompute(self.h, self._ptr(importances), importances.numel(), self._ptr(indices_out),
                                                   self._ptr(n_changed), self._stream()))
 
+    def update_budget(self, n_photons: int, percent: float) -> int:
+        """Photons one evaluation may re-trace: (int)((percent / 100.f) * (float)n_photons), the reference's float arithmetic."""
+        return int(self.lib.cpm_update_budget(n_photons, percent))
+
     # -- the correlated update without a host round trip
     def selection_create(self, max_photons: int) -> "Selection":
         h = C.c_void_p()
@@ -1001,9 +1010,25 @@ class Selection:
         c._check(c.lib.cpm_photon_importance_equal_select(c.h, self.h, photon_offset, n_light_samples, percentage, iteration,
                                                           c._ptr(importances), c._stream()))
 
-    def finish(self, indices_out):
+    def select_pending(self, importances, photon_offset, n_light_samples):
+        """A continuation's selection: lists the photons of one light whose key is still below 0x7fffffff; no key is written."""
         c = self.ctx
-        c._check(c.lib.cpm_selection_finish(c.h, self.h, c._ptr(indices_out), c._stream()))
+        c._check(c.lib.cpm_selection_select_pending(c.h, self.h, c._ptr(importances), photon_offset, n_light_samples, c._stream()))
+
+    def finish(self, indices_out, budget=None, importances=None):
+        """budget=None: every selected photon, ascending.  Otherwise the `budget` most important of them (smallest key in
+        `importances`, ties by index), ascending: cpm_selection_finish_budget."""
+        c = self.ctx
+        if budget is None:
+            c._check(c.lib.cpm_selection_finish(c.h, self.h, c._ptr(indices_out), c._stream()))
+        else:
+            c._check(c.lib.cpm_selection_finish_budget(c.h, self.h, c._ptr(importances), budget, c._ptr(indices_out), c._stream()))
+
+    def counts(self):
+        """(listed, changed) of the last finish(), read from its host mailbox (no stream synchronisation)."""
+        m, n = C.c_int32(0), C.c_int32(0)
+        self.ctx._check(self.ctx.lib.cpm_selection_counts(self.ctx.h, self.h, C.byref(m), C.byref(n)))
+        return int(m.value), int(n.value)
 
     def count(self) -> int:
         """The count of the last finish(), read from its host mailbox (no stream synchronisation)."""

@@ -2,39 +2,12 @@
 // temporal difference bricks, TF-difference importance per brick, per-photon importance by
 // DDA through the importance grid, and the fused threshold + count + iota + sort selection.
 #include "cpm_trace_body.hip.h"
+#include "cpm_selection.h"
 
 #include <chrono>
 #include <new>
 
 using namespace cpm;
-
-// cpm_selection (include/cpm/cpm.h): the state of one changed-photon selection
-struct cpm_selection {
-    size_t max_photons = 0;
-    uint32_t per_tile = 0, max_tiles = 0;
-    uint2* tile = nullptr;            // device, max_tiles
-    uint32_t* local = nullptr;        // device, max_photons
-    int32_t* count_dev = nullptr;     // device
-    uint32_t* mask = nullptr;         // device, grow-only: occupancy bits of the importance grid of the last select call
-    size_t mask_words = 0;
-    const uint32_t* given_mask = nullptr;  // cpm_selection_set_occupancy: the caller's bits (cpm_importance_tf_occupancy) ...
-    const float* given_mask_grid = nullptr;  // ... of this importance grid
-    unsigned long long* mailbox = nullptr;      // pinned host memory, written by selection_compact_kernel
-    unsigned long long* mailbox_dev = nullptr;  // its device address
-    uint32_t n_tiles = 0;             // tiles appended since cpm_selection_begin
-    // cpm_photon_importance_retrace: per launch since cpm_selection_begin (one per light) the order in which its workgroups
-    // take the tiles -- costliest first, from the wall-clock the tiles took in the last MEASURED launch (see kRetraceTile)
-    struct LaunchOrder { uint32_t n_tiles = 0; uint32_t* order = nullptr; uint32_t* cost = nullptr; uint32_t* keys = nullptr; bool fresh = true; /* no order yet */ };
-    std::vector<LaunchOrder> orders;
-    std::vector<uint32_t> pending_orders;  // launches measured in this selection: their orders are re-sorted by cpm_selection_finish
-    uint32_t n_launches = 0;          // retrace launches since cpm_selection_begin
-    uint32_t selections = 0;          // cpm_selection_begin calls
-    bool measuring = false;           // this selection's retrace launches record what their tiles cost
-    uint32_t epoch = 0;               // of the last cpm_selection_finish enqueued
-    bool finished = false;            // a finish has been enqueued since begin
-    bool failed = false;              // a select / retrace call since begin failed after its tiles were appended: the finish publishes 0
-    hipStream_t last_stream = nullptr;
-};
 
 namespace {
 
@@ -533,7 +506,8 @@ struct SelTiles {
     uint32_t per_tile;    // photons per tile = 256 * K
 };
 
-// MODE 0: importance by DDA through the grid (mask staged in LDS when MASK); MODE 1: the equal-importance rule.
+// MODE 0: importance by DDA through the grid (mask staged in LDS when MASK); MODE 1: the equal-importance rule; MODE 2: no
+// importance pass at all -- the keys as they are (cpm_selection_select_pending: nothing is written to them).
 // One workgroup = one tile of K * 256 consecutive light samples; thread t takes samples b0 + k * 256 + t.  Importances are
 // updated as by photon_importance_kernel; the photons whose key is then < 0x7fffffff are ranked with ballots (ascending
 // sample index) and listed at the tile's own place -- no atomics, no global prefix: cpm_selection_finish lines the tiles up.
@@ -563,9 +537,11 @@ __global__ __launch_bounds__(256) void importance_select_kernel(ImpGrid G, const
             uint32_t u;
             if (MODE == 0) {
                 u = photon_importance_value<MASK>(G, s_mask, photons, photon_offset, ls, isect, max_interactions, total_photons, fix_exit_point, threadId);
-            } else {
+            } else if (MODE == 1) {
                 const int photonId = photon_offset + threadId;
                 u = ((photonId + eq_iteration) % (100 / eq_percentage) == 0) ? importance_to_uint(100.f * 1.f) : importance_to_uint(100.f * 0.f);
+            } else {
+                u = 0u;
             }
             uint32_t key = importances[photon_offset + threadId];
             if (u != 0u) { key -= u; importances[photon_offset + threadId] = key; }   // (key -= 0 leaves the word as it is)
@@ -597,7 +573,6 @@ __global__ __launch_bounds__(256) void importance_select_kernel(ImpGrid G, const
 // loads, no scan launch), copies its list behind them; workgroup 0 also publishes the total -- the device word the
 // following launches read and the pinned host mailbox (epoch << 32 | count) the host polls instead of synchronising.
 // (A workgroup takes kCompactGroup tiles: with one tile each, 4096 tiles of 256 photons meant 16 M count loads -- 13 us.)
-constexpr uint32_t kCompactGroup = 16;  // tiles per workgroup of selection_compact_kernel
 __global__ __launch_bounds__(256) void selection_compact_kernel(const uint2* __restrict__ tile, uint32_t n_tiles,
                                                                 const uint32_t* __restrict__ local, uint32_t* __restrict__ indices,
                                                                 int32_t* __restrict__ count_dev, unsigned long long* mailbox, uint32_t epoch) {
@@ -621,6 +596,8 @@ __global__ __launch_bounds__(256) void selection_compact_kernel(const uint2* __r
     total = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     if (blockIdx.x == 0 && t == 0) {
         *count_dev = (int32_t)total;
+        // (word 1 = the changed photons, word 0 = the listed ones: the same number here; cpm_selection_counts reads 0, then 1)
+        __hip_atomic_store(mailbox + 1, ((unsigned long long)epoch << 32) | (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(mailbox, ((unsigned long long)epoch << 32) | (unsigned long long)total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (t == 0) {
@@ -1142,6 +1119,8 @@ int cpm_selection_create(cpm_ctx* ctx, size_t max_photons, cpm_selection** out) 
     bool ok = hipMalloc(&s->tile, (size_t)s->max_tiles * sizeof(uint2)) == hipSuccess &&
               hipMalloc(&s->local, max_photons * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&s->count_dev, sizeof(int32_t)) == hipSuccess &&
+              hipMalloc(&s->budget_hist, kBudgetHistWords * sizeof(uint32_t)) == hipSuccess &&
+              hipMalloc(&s->budget_group, (size_t)div_up(s->max_tiles, kCompactGroup) * sizeof(uint2)) == hipSuccess &&
               hipHostMalloc(&s->mailbox, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
               hipHostGetDevicePointer((void**)&s->mailbox_dev, s->mailbox, 0) == hipSuccess &&
               hipMemset(s->count_dev, 0, sizeof(int32_t)) == hipSuccess;
@@ -1150,7 +1129,7 @@ int cpm_selection_create(cpm_ctx* ctx, size_t max_photons, cpm_selection** out) 
         cpm_selection_destroy(ctx, s);
         return set_error(ctx, CPM_ERR_OUT_OF_MEMORY, "cpm_selection_create", "device / pinned allocation");
     }
-    *s->mailbox = 0ull;
+    s->mailbox[0] = s->mailbox[1] = 0ull;
     *out = s;
     return CPM_OK;
 }
@@ -1162,6 +1141,8 @@ void cpm_selection_destroy(cpm_ctx* ctx, cpm_selection* s) {
     if (s->tile) (void)hipFree(s->tile);
     if (s->local) (void)hipFree(s->local);
     if (s->count_dev) (void)hipFree(s->count_dev);
+    if (s->budget_hist) (void)hipFree(s->budget_hist);
+    if (s->budget_group) (void)hipFree(s->budget_group);
     for (auto& o : s->orders) {
         if (o.order) (void)hipFree(o.order);
         if (o.cost) (void)hipFree(o.cost);
@@ -1185,6 +1166,7 @@ int cpm_selection_begin(cpm_ctx* ctx, cpm_selection* s) {
     CPM_ENTER(ctx);
     CPM_REQUIRE(ctx, s, "cpm_selection_begin: null selection");
     s->n_tiles = 0;
+    s->appended_photons = 0;
     s->n_launches = 0;
     s->pending_orders.clear();
     s->finished = false;
@@ -1209,6 +1191,7 @@ int selection_append(cpm_ctx* ctx, cpm_selection* s, int photon_offset, int n_li
     CPM_REQUIRE(ctx, s->n_tiles + *tiles <= s->max_tiles, "cpm_photon_importance_select: too many lights for this selection");
     *first = s->n_tiles;
     s->n_tiles += *tiles;
+    s->appended_photons += (size_t)n_light_samples;
     return CPM_OK;
 }
 
@@ -1216,7 +1199,7 @@ int selection_append(cpm_ctx* ctx, cpm_selection* s, int photon_offset, int n_li
 // selection_compact_kernel (it would sum uninitialised counts and copy garbage indices).  A selection with a failed call is
 // marked: cpm_selection_finish then publishes a count of 0 and reports the failure.
 struct AppendGuard {
-    cpm_selection* s; uint32_t n_tiles0, n_launches0; bool ok = false;
+    cpm_selection* s; uint32_t n_tiles0, n_launches0; bool ok = false;   // (appended_photons is an upper bound only: left as it is)
     AppendGuard(cpm_selection* sel, uint32_t first) : s(sel), n_tiles0(first), n_launches0(sel->n_launches) {}
     ~AppendGuard() { if (!ok) { s->n_tiles = n_tiles0; s->n_launches = n_launches0; s->failed = true; } }
 };
@@ -1525,6 +1508,30 @@ int cpm_photon_importance_equal_select(cpm_ctx* ctx, cpm_selection* s, int photo
     ImpGrid G = {};
     launch_select<1, false>(ctx, s, st, tiles, 0, G, nullptr, 0u, nullptr, photon_offset, nullptr, nullptr, n_light_samples, 1, 0, 0, percentage, iteration,
                             importances, S);
+    CPM_LAUNCH_CHECK(ctx, "importance_select_kernel");
+    guard.ok = true;
+    return CPM_OK;
+}
+
+int cpm_selection_select_pending(cpm_ctx* ctx, cpm_selection* s, const uint32_t* importances, int photon_offset, int n_light_samples,
+                                 cpm_stream stream) {
+    CPM_ENTER(ctx);
+    CPM_REQUIRE(ctx, s, "cpm_selection_select_pending: null selection");
+    CPM_REQUIRE(ctx, n_light_samples >= 0 && photon_offset >= 0, "cpm_selection_select_pending: bad size");
+    if (n_light_samples == 0) return CPM_OK;
+    CPM_REQUIRE(ctx, importances, "cpm_selection_select_pending: null buffer");
+    uint32_t first = 0, tiles = 0;
+    int rc = selection_append(ctx, s, photon_offset, n_light_samples, &first, &tiles);
+    if (rc) return rc;
+    AppendGuard guard(s, first);
+    CPM_INJECTED_SELECT_FAILURE(ctx, "cpm_selection_select_pending");
+    hipStream_t st = (hipStream_t)stream;
+    s->last_stream = st;
+    SelTiles S{ s->tile, s->local, first, s->per_tile };
+    ImpGrid G = {};
+    // (MODE 2 never stores to the keys: the kernel's pointer is non-const for the other modes' sake)
+    launch_select<2, false>(ctx, s, st, tiles, 0, G, nullptr, 0u, nullptr, photon_offset, nullptr, nullptr, n_light_samples, 1, 0, 0, 1, 0,
+                            const_cast<uint32_t*>(importances), S);
     CPM_LAUNCH_CHECK(ctx, "importance_select_kernel");
     guard.ok = true;
     return CPM_OK;

@@ -207,6 +207,8 @@ int cpmh_download_photons(cpmh_network* net, float* out) {
 }
 int cpmh_n_recomputed(cpmh_network* net) { auto r = net->tracer.recomputedIndicesPort_.getData(); return r ? r->resolveCount() : -1; }
 int cpmh_remaining(cpmh_network* net) { return net->tracer.remainingPhotonsToUpdate(); }
+// times the tracer blocked on a device count between its importance pass and its trace (0 for the device-resident branches)
+int cpmh_tracer_host_waits(cpmh_network* net) { return net->tracer.hostWaits(); }
 const char* cpmh_last_light_volume_path(cpmh_network* net) { return net->lightVolume.lastPath(); }
 const char* cpmh_last_tracer_decision(cpmh_network* net) { return net->tracer.lastDecision(); }
 // measured GPU-timeline cost of the two ways to serve a change: { full trace, full light volume, branch trace, branch light volume } ms (-1 = not measured yet)

@@ -426,8 +426,11 @@ bool PhotonTracerCL::tracePhotonsAllLights(const Volume* volume, const TransferF
 int RecomputedPhotonIndices::resolveCount() {
     if (countPending && selection) {
         auto& rt = CpmRuntime::get();
-        int32_t n = 0;
-        if (rt.check(cpm_selection_count(rt.ctx(), selection, &n), "cpm_selection_count")) nRecomputedPhotons = n;
+        int32_t n = 0, changed = 0;
+        if (rt.check(cpm_selection_counts(rt.ctx(), selection, &n, &changed), "cpm_selection_counts")) {
+            nRecomputedPhotons = n;
+            nPendingPhotons = changed - n;
+        }
         countPending = false;
         const size_t total = indicesToRecomputedPhotons.getSize();
         if (costs && total > 0 && n >= 0) costs->sawFraction((float)n / (float)total);
@@ -781,7 +784,7 @@ ProgressivePhotonTracerCL::ProgressivePhotonTracerCL() {
     for (PropertyBase* p : std::initializer_list<PropertyBase*>{ &samplingRate_, &radius_, &sceneRadianceScaling_, &maxIncrementalPhotonsToUpdate_,
                                                                 &equalIncrementalImportance_, &spatialSorting_, &maxScatteringEvents_, &noSingleScattering_,
                                                                 &alphaProp_, &workGroupSize_, &useGLSharing_, &enableProgressiveRefinement_,
-                                                                &enableProgressivePhotonRecomputation_, &clipX_, &clipY_, &clipZ_, &fusedImportanceBranch_,
+                                                                &enableProgressivePhotonRecomputation_, &clipX_, &clipY_, &clipZ_, &fusedImportanceBranch_, &budgetOnDevice_,
                                                                 &equalImportancePercentage_, &importanceBranchPolicy_, &retraceInImportancePass_, &traceLightsInOneLaunch_ })
         addProperty(*p);
     addProperty(advancedMaterial_); addProperty(camera_); addProperty(invalidateRendering_); addProperty(transferFunctionProperty_);
@@ -822,15 +825,25 @@ void ProgressivePhotonTracerCL::resetPhotonImportance(size_t offset, size_t n) {
     rt.check(cpm_reset_importance(rt.ctx(), photonRecomputationImportance_.device(), offset, n, rt.stream()), "cpm_reset_importance");
     if (whole) importancesAreReset_ = true;
 }
+void ProgressivePhotonTracerCL::syncRemaining() {
+    if (!remainingPending_) return;
+    remainingPending_ = false;
+    recomputedPhotonIndices_->resolveCount();
+    const int budget = cpm_update_budget(photonData_->getNumberOfPhotons(), maxIncrementalPhotonsToUpdate_.get());
+    // (a budget of no photon at all would leave them pending for ever)
+    remainingPhotonsToUpdate_ = budget > 0 ? std::max(0, recomputedPhotonIndices_->nPendingPhotons) : 0;
+    enableProgressiveRefinement_.set(remainingPhotonsToUpdate_ > 0 && enableProgressivePhotonRecomputation_.get());
+}
 void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:219-605
     auto& rt = CpmRuntime::get();
     if (!photonTracer_.isValid() || !volumePort_.isReady()) return;
+    syncRemaining();
     rt.beginProfile();
     span_.poll();
     photonTracer_.syncTF(transferFunction_);  // the LUT upload goes first: nothing waits for it later
     if (volumePort_.changedSinceLastCheck()) invalidateProgressiveRendering(PhotonData::InvalidationReason::Volume);  // volumePort_.onChange (:107-108)
     recomputedPhotonIndices_->costs = &costs_;
-    recomputedPhotonIndices_->keepsReplaced = fusedImportanceBranch_.get() && maxIncrementalPhotonsToUpdate_.get() >= 100.f &&
+    recomputedPhotonIndices_->keepsReplaced = fusedImportanceBranch_.get() && (maxIncrementalPhotonsToUpdate_.get() >= 100.f || budgetOnDevice_.get()) &&
                                               recomputationImportanceGrid_.isConnected();
     const auto lights = lightSamples_.getVectorData();
     size_t nPhotons = 0;
@@ -897,13 +910,18 @@ void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:21
         // The whole branch with the count kept on the device (cpm.h, "the correlated update without a host round trip"):
         // possible when every changed photon is traced in this evaluation -- a budget below 100 % needs the ranking by
         // importance, a host decision on the count.
-        bool fused = fusedImportanceBranch_.get() && (flag & (tfFlag | volFlag)) && maxIncrementalPhotonsToUpdate_.get() >= 100.f;
+        // With budgetOnDevice a smaller budget stays on the device as well: the ranking is a selection by rank there
+        // (cpm_selection_finish_budget), and an evaluation without a TF / volume flag -- the refinement timer's -- continues with
+        // the photons whose keys say they are still pending.
+        const bool budgeted = fusedImportanceBranch_.get() && budgetOnDevice_.get() && maxIncrementalPhotonsToUpdate_.get() < 100.f;
+        const bool continuation = budgeted && !(flag & (tfFlag | volFlag)) && remainingPhotonsToUpdate_ > 0;
+        bool fused = fusedImportanceBranch_.get() && (((flag & (tfFlag | volFlag)) && (maxIncrementalPhotonsToUpdate_.get() >= 100.f || budgeted)) || continuation);
         // The branch exists to avoid re-tracing everything; where its measured cost (importance pass over ALL photons, re-trace,
         // add-remove) exceeds the full frame's, take the frame: the correlated RNG streams make the photons the same either way.
         bool takeFullFrame = false;
-        if (fused && importanceBranchPolicy_.get() == "never") {
+        if (fused && !continuation && importanceBranchPolicy_.get() == "never") {
             takeFullFrame = true;
-        } else if (fused && importanceBranchPolicy_.get() == "adaptive") {
+        } else if (fused && !continuation && importanceBranchPolicy_.get() == "adaptive") {
             auto& c = costs_;
             const bool fullFrameCheaper = c.known() && c.branchTraceMs() + c.branchLightVolumeMs() > c.fullTraceMs + c.fullLightVolumeMs;
             c.probing = false;
@@ -939,7 +957,8 @@ void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:21
         }
         recomputedPhotonIndices_->takenInPlaceOfBranch = false;
         if (fused) {
-            lastDecision_ = "importance branch";
+            lastDecision_ = continuation ? "importance branch continuation (budget on device)" : budgeted ? "importance branch (budget on device)" : "importance branch";
+            const int budget = budgeted ? cpm_update_budget(photonData_->getNumberOfPhotons(), maxIncrementalPhotonsToUpdate_.get()) : 0;
             span_.begin(rt.stream(), &costs_.branchTraceMs(), costs_.probing);
             auto grid = std::dynamic_pointer_cast<ImportanceUniformGrid3D>(recomputationImportanceGrid_.getData());
             if (!grid) { LogError("UniformGrid3DInport require ImportanceUniformGrid3D as input"); return; }
@@ -952,11 +971,14 @@ void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:21
             }
             auto& rec = *recomputedPhotonIndices_;
             if (rec.replacedPhotons.getSize() != photonData_->photons_.getSize()) rec.replacedPhotons.setSize(photonData_->photons_.getSize());
-            photonRecomputationDetector_.setPercentage(equalImportancePercentage_.get() > 0 ? equalImportancePercentage_.get() : (int)maxIncrementalPhotonsToUpdate_.get());
-            photonRecomputationDetector_.setIteration(photonRecomputationDetector_.getIteration() + 1);
+            if (!continuation) {
+                photonRecomputationDetector_.setPercentage(equalImportancePercentage_.get() > 0 ? equalImportancePercentage_.get() : (int)maxIncrementalPhotonsToUpdate_.get());
+                photonRecomputationDetector_.setIteration(photonRecomputationDetector_.getIteration() + 1);
+            }
             rt.check(cpm_selection_begin(rt.ctx(), selection_), "cpm_selection_begin");
             importancesAreReset_ = false;  // the importance pass below lowers the keys
-            const bool oneLaunch = retraceInImportancePass_.get() && !photonRecomputationDetector_.getEqualImportance() &&
+            // (detector and tracer in one launch cannot serve a budget: the choice must precede the trace)
+            const bool oneLaunch = !budgeted && retraceInImportancePass_.get() && !photonRecomputationDetector_.getEqualImportance() &&
                                    !photonTracer_.isProgressive();
             int offset = 0;
             // A selection one of whose launches failed publishes a count of 0 (cpm_selection_finish reports it): nothing behind
@@ -981,12 +1003,20 @@ void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:21
                 }
                 selected &= rt.check(cpm_selection_finish(rt.ctx(), selection_, rec.indicesToRecomputedPhotons.device(), rt.stream()), "cpm_selection_finish");
             } else {
-                for (auto& l : lights) {  // detector + threshold + count + index lists, per light (:298-356)
-                    selected &= photonRecomputationDetector_.photonRecomputationImportanceSelect(selection_, photonData_.get(), offset, volume, grid.get(), *l,
-                                                                                                 photonRecomputationImportance_, fixExitPoint);
+                for (auto& l : lights) {  // detector + threshold + count + index lists, per light (:298-356); a continuation: the pending photons' lists
+                    if (continuation)
+                        selected &= rt.check(cpm_selection_select_pending(rt.ctx(), selection_, photonRecomputationImportance_.device(), offset, (int)l->getSize(),
+                                                                          rt.stream()), "cpm_selection_select_pending");
+                    else
+                        selected &= photonRecomputationDetector_.photonRecomputationImportanceSelect(selection_, photonData_.get(), offset, volume, grid.get(), *l,
+                                                                                                     photonRecomputationImportance_, fixExitPoint);
                     offset += (int)l->getSize();
                 }
-                selected &= rt.check(cpm_selection_finish(rt.ctx(), selection_, rec.indicesToRecomputedPhotons.device(), rt.stream()), "cpm_selection_finish");
+                if (budgeted)  // the budget's most important of them (sortIndicesByImportance + the host's min(count, budget), :358-419)
+                    selected &= rt.check(cpm_selection_finish_budget(rt.ctx(), selection_, photonRecomputationImportance_.device(), budget,
+                                                                     rec.indicesToRecomputedPhotons.device(), rt.stream()), "cpm_selection_finish_budget");
+                else
+                    selected &= rt.check(cpm_selection_finish(rt.ctx(), selection_, rec.indicesToRecomputedPhotons.device(), rt.stream()), "cpm_selection_finish");
             }
             if (!selected) {
                 span_.end(rt.stream());
@@ -994,11 +1024,12 @@ void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:21
                 fullFrameInPlaceOfBranch("full frame (the importance branch failed)");
                 return;
             }
-            if (!oneLaunch) {
+            const int maxSelected = budgeted ? budget : (int)N;  // what the list may hold: the launches behind it cover that many
+            if (!oneLaunch && maxSelected > 0) {
                 offset = 0;
                 for (auto& l : lights) {  // ascending indices = emission-lattice order (:467-473); importance reset in the same launch (:529)
                     photonTracer_.tracePhotonsSelected(volume, transferFunction_, aabb_, advancedMaterial_, stepSize, l.get(), &rec.indicesToRecomputedPhotons,
-                                                       cpm_selection_count_device(selection_), (int)N, rec.replacedPhotons.device(),
+                                                       cpm_selection_count_device(selection_), maxSelected, rec.replacedPhotons.device(),
                                                        photonRecomputationImportance_.device(), offset, maxInteractions, photonData_.get());
                     offset += (int)l->getSize();
                 }
@@ -1007,12 +1038,13 @@ void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:21
             rec.selection = selection_;
             rec.countPending = true;
             rec.nRecomputedPhotons = 0;  // resolved on first use (resolveCount)
-            rec.replacedStride = oneLaunch ? 0 : (int)N;  // 0: the replaced records sit at the photons' own indices
+            rec.replacedStride = oneLaunch ? 0 : maxSelected;  // 0: the replaced records sit at the photons' own indices
             rec.replacedValid = true;
             rankedByImportance_ = false;
             remainingPhotonsOffset_ = 0;
-            remainingPhotonsToUpdate_ = 0;  // everything changed was traced
+            remainingPhotonsToUpdate_ = 0;  // everything changed was traced ...
             enableProgressiveRefinement_.set(false);
+            remainingPending_ = budgeted;   // ... or what the budget left arrives with the count (syncRemaining)
             publishPhotons();
             if (rt.profiling()) {
                 rt.logProfile("Photon tracing");
@@ -1041,6 +1073,7 @@ void ProgressivePhotonTracerCL::process() {  // progressivephotontracercl.cpp:21
                                         recomputedPhotonIndices_->indicesToRecomputedPhotons.device(), nChanged_.device(), rt.stream()),
                      "cpm_select_changed");
             nChanged_.download(rt.stream());
+            ++hostWaits_;
             const int nPhotonsToRecompute = nChanged_.ram()[0];
             const int budget = (int)((maxIncrementalPhotonsToUpdate_.get() / 100.f) * (float)photonData_->getNumberOfPhotons());
             rankedByImportance_ = nPhotonsToRecompute > budget;
@@ -1164,6 +1197,8 @@ void PhotonToLightVolumeProcessorCL::process() {  // photontolightvolumeprocesso
     // (apply_below) -- so it is enqueued FIRST, and only then does the host read the count (its pinned mailbox, not the
     // stream): the launch is already queued behind the tracer's when the count arrives, instead of being launched into an idle
     // GPU after it (8 - 10 us of every update).
+    // (the list holds at most replacedStride photons when the tracer kept their records in list order: a budgeted evaluation's stride is its budget)
+    const int maxListed = (haveIdx && rec->replacedStride > 0) ? std::min(rec->replacedStride, nPhotons) : nPhotons;
     bool deltaEnqueued = false;
     if (haveIdx && rec->countPending && useReplaced && !fresh && maxRecomputationPhotons > 0) {
         if (rec->costs) span_.begin(rt.stream(), &rec->costs->branchLightVolumeMs(), rec->costs->probing);
@@ -1175,7 +1210,7 @@ void PhotonToLightVolumeProcessorCL::process() {  // photontolightvolumeprocesso
             mask = brickMask_.device();
         }
         deltaEnqueued = rt.check(cpm_splat_delta(rt.ctx(), reinterpret_cast<const float*>(rec->replacedPhotons.device()), rec->replacedStride, photons,
-                                                 rec->indicesToRecomputedPhotons.device(), rec->countDevice(), nPhotons, maxRecomputationPhotons, &g, radius,
+                                                 rec->indicesToRecomputedPhotons.device(), rec->countDevice(), maxListed, maxRecomputationPhotons, &g, radius,
                                                  scale, nPhotons, nInter, mask, out, rt.stream()), "cpm_splat_delta");
     }
     const int nRecomputed = haveIdx ? rec->resolveCount() : -1;
@@ -1230,7 +1265,7 @@ void PhotonToLightVolumeProcessorCL::process() {  // photontolightvolumeprocesso
                 marksDone = true;
             }
             rt.check(cpm_splat_delta(rt.ctx(), reinterpret_cast<const float*>(rec->replacedPhotons.device()), rec->replacedStride, photons, idx,
-                                     rec->countDevice(), nPhotons, 0, &g, radius, scale, nPhotons, nInter, mask, out, rt.stream()), "cpm_splat_delta");
+                                     rec->countDevice(), maxListed, 0, &g, radius, scale, nPhotons, nInter, mask, out, rt.stream()), "cpm_splat_delta");
             lastPath_ = "incremental";
         } else {
         // add-remove (:196-298): -old, +new over the re-traced photons

@@ -104,6 +104,9 @@ struct RecomputedPhotonIndices {
     cpm_selection* selection = nullptr;
     bool countPending = false;
     int resolveCount();
+    // a budgeted evaluation (cpm_selection_finish_budget) lists only the budget's most important photons: what it left pending,
+    // known with the count (the same mailbox poll)
+    int nPendingPhotons = 0;
     const int32_t* countDevice() const { return selection ? cpm_selection_count_device(selection) : nullptr; }
     // ... and the tracer keeps the records it overwrites: replacedPhotons[k * replacedStride + j] is what photon
     // indicesToRecomputedPhotons[j] was at interaction k before this evaluation -- the part of the light-volume processor's
@@ -518,7 +521,10 @@ public:
     // ref :647-651: the tracer writes its RNG state back only when refinement is on and no importance grid is connected
     void progressiveRefinementChanged() { photonTracer_.setProgressive(enableProgressiveRefinement_.get() && !recomputationImportanceGrid_.isConnected()); }
     void setTransferFunction(const TransferFunction& tf) { transferFunction_ = tf; invalidateProgressiveRendering(PhotonData::InvalidationReason::TransferFunction); }
-    int remainingPhotonsToUpdate() const { return remainingPhotonsToUpdate_; }
+    // (after a budgeted evaluation on the device the number arrives with the count: picked up here, a poll of the mailbox)
+    int remainingPhotonsToUpdate() { syncRemaining(); return remainingPhotonsToUpdate_; }
+    // host reads of a device count the tracer blocked on between its importance pass and its trace, since construction
+    int hostWaits() const { return hostWaits_; }
 
     DataInport<Volume> volumePort_{ "volume" };
     DataInport<UniformGrid3DBase> recomputationImportanceGrid_{ "recomputationImportance" };
@@ -552,9 +558,13 @@ public:
     // and cpm_trace_selected as separate launches (still no host round trip).  The equal-importance detector takes the latter.
     BoolProperty retraceInImportancePass_{ "retraceInImportancePass", "Re-trace inside the importance pass", true };
     BoolProperty traceLightsInOneLaunch_{ "traceLightsInOneLaunch", "Full frames trace all lights in one launch", true };
-    // false: the importance branch launch by launch with its host read of the count in the middle (always taken when the update
-    // budget is below 100 %: ranking by importance is a host decision); true (default): the count stays on the device
+    // false: the importance branch launch by launch with its host read of the count in the middle (also taken when the update
+    // budget is below 100 % unless budgetOnDevice is set); true (default): the count stays on the device
     BoolProperty fusedImportanceBranch_{ "fusedImportanceBranch", "Importance branch without host round trip", true };
+    // true: a budget below 100 % keeps the count on the device too -- the budget's most important changed photons are chosen by
+    // cpm_selection_finish_budget, the keys stay at the photons' own indices and the timer's continuation lists what is still
+    // pending (cpm_selection_select_pending); false (default): such a budget takes the launch-by-launch chain with its host decision
+    BoolProperty budgetOnDevice_{ "budgetOnDevice", "Update budget chosen on the device", false };
     // "adaptive": where the measured cost of importance branch + add-remove exceeds that of re-tracing and rebuilding
     // everything (CpmRuntime::PathCosts), a TF / volume change is served by the full frame -- the same photons (correlated RNG
     // streams), the same light volume within the add-remove tolerance; the branch is measured again every 32nd such evaluation.
@@ -587,6 +597,9 @@ private:
     PhotonData::InvalidationReason invalidationFlag_ = PhotonData::InvalidationReason::All;
     float aabb_[8] = { 0, 0, 0, 1, 1, 1, 1, 1 };
     int remainingPhotonsOffset_ = 0, remainingPhotonsToUpdate_ = -1;
+    bool remainingPending_ = false;  // the last evaluation was budgeted on the device: remainingPhotonsToUpdate_ comes with its count
+    int hostWaits_ = 0;
+    void syncRemaining();
     bool rankedByImportance_ = true;  // indices / importances are sorted by importance (cpm_select_recompute ran)
     std::vector<std::pair<const LightSamples*, size_t>> seenLights_;  // (samples, change stamp) at the last evaluation
 };

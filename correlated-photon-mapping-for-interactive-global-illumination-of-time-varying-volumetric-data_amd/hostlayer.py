@@ -24,6 +24,10 @@ def load():
         "cpmh_set_property_string": (i32, [vp, C.c_char_p, C.c_char_p, C.c_char_p]),
         "cpmh_n_photons": (i32, [vp]),
         "cpmh_n_recomputed": (i32, [vp]),
+        "cpmh_remaining": (i32, [vp]),
+        "cpmh_refine": (i32, [vp]),
+        "cpmh_tracer_host_waits": (i32, [vp]),
+        "cpmh_download_photons": (i32, [vp, vp]),
         "cpmh_last_light_volume_path": (C.c_char_p, [vp]),
         "cpmh_last_tracer_decision": (C.c_char_p, [vp]),
         "cpmh_path_costs": (None, [vp, vp]),
@@ -62,6 +66,7 @@ class HostNetwork:
         self.lib = lib
         vol = np.ascontiguousarray(volume_u8)
         pts = np.ascontiguousarray(np.asarray(tf_points, np.float32))
+        self.max_scattering = max_scattering
         self.h = lib.cpmh_create(vol.ctypes.data, B._np_dtype_code(vol.dtype), vol.shape[2], vol.shape[1], vol.shape[0], n_side, n_side,
                                  C.byref((C.c_float * 3)(*light_position)), C.byref((C.c_float * 3)(*light_direction)),
                                  pts.ctypes.data, pts.shape[0], size_option, max_scattering, int(correlated))
@@ -79,6 +84,37 @@ class HostNetwork:
     def set_string(self, processor: str, prop: str, value: str):
         if self.lib.cpmh_set_property_string(self.h, processor.encode(), prop.encode(), value.encode()) != 0:
             raise KeyError(f"{processor}.{prop}")
+
+    def set_transfer_function(self, tf_points):
+        pts = np.ascontiguousarray(np.asarray(tf_points, np.float32))
+        self.lib.cpmh_set_transfer_function(self.h, pts.ctypes.data, pts.shape[0])
+
+    def refine(self):
+        """One firing of the refinement timer and the evaluation it causes (a pending correlated update continues with its next batch)."""
+        if self.lib.cpmh_refine(self.h) < 0:
+            raise RuntimeError("cpmh_refine failed")
+
+    @property
+    def n_recomputed(self):
+        """Photons the last evaluation re-traced (-1: all of them)."""
+        return int(self.lib.cpmh_n_recomputed(self.h))
+
+    @property
+    def remaining(self):
+        """Changed photons the update budget has left for the timer's evaluations."""
+        return int(self.lib.cpmh_remaining(self.h))
+
+    @property
+    def host_waits(self):
+        """Times the tracer has blocked on a device count between its importance pass and its trace."""
+        return int(self.lib.cpmh_tracer_host_waits(self.h))
+
+    def photons(self):
+        """The photon records, (I * N, 8) float32, interaction by interaction."""
+        out = np.zeros((self.n_photons * self.max_scattering, 8), np.float32)
+        if self.lib.cpmh_download_photons(self.h, out.ctypes.data) != 0:
+            raise RuntimeError("cpmh_download_photons failed")
+        return out
 
     @property
     def n_photons(self):

@@ -453,8 +453,13 @@ class CorrelatedPhotonMapper(PhotonFrame):
 
     def __init__(self, *args, region: int = 8, max_incremental_percent: float = 100.0,
                  incremental_threshold_percent: float = 50.0, fix_exit_point: bool = False, tf_points=None,
-                 exact_update: bool = False, formulation: str = "fast", **kw):
+                 exact_update: bool = False, formulation: str = "fast", device_budget: bool = False,
+                 detector: str = "importance", equal_percentage: int = 10, **kw):
         super().__init__(*args, **kw)
+        if detector not in ("importance", "equal"):
+            raise ValueError("detector: 'importance' or 'equal'")
+        if detector == "equal" and not (device_budget and max_incremental_percent < 100.0 and not exact_update and self.emitter is None):
+            raise ValueError("detector='equal' is served by the budgeted device path only (device_budget=True, a budget below 100 %)")
         # full light volumes: "fast" = brick bin + one-launch gather (tolerance mode; the reference's own update is two atomic
         # splats on top of it, within the same tolerance), "exact" = cell sort + sequential gather -- forced by exact_update,
         # whose touched-brick re-gather must land on a full gather's bits
@@ -492,6 +497,18 @@ class CorrelatedPhotonMapper(PhotonFrame):
         self.selection = None
         self.old_photons = None
         self.fused = True
+        # device_budget: a budget below 100 % takes the device-resident update too -- the budget's most important changed photons are
+        # chosen on the device (cpm_selection_finish_budget), the keys stay at the photons' own indices, continue_update lists what
+        # is still pending (cpm_selection_select_pending).  Off: such a budget takes the legacy chain with its host decision.
+        # (The device path's budget is cpm_update_budget's float32 arithmetic, the reference's; the legacy chain below computes
+        # int((pct / 100.0) * n) in double, which for percentages such as 33.3 can differ by one photon.)
+        self.device_budget = device_budget
+        # "equal": the equal-importance detector (every equal_percentage-th photon, rotating with the evaluation) in place of the
+        # walk through the importance grid -- budgeted device path only
+        self.detector = detector
+        self.equal_percentage = equal_percentage
+        self._equal_iteration = 0
+        self.n_changed_last = -1                 # |C| of the last budgeted evaluation (changed or still pending before it)
         self.retrace_in_importance_pass = True   # cpm_photon_importance_retrace (False: select, compact, then cpm_trace_selected)
 
     def full_frame(self):
@@ -582,15 +599,21 @@ class CorrelatedPhotonMapper(PhotonFrame):
         self.minmax, self._minmax_next = self._minmax_next, self.minmax
 
     def _fused_configured(self):
-        return self.fused and not self.exact_update and self.max_incremental_percent >= 100.0 and self.emitter is None
+        return (self.fused and not self.exact_update and (self.max_incremental_percent >= 100.0 or self.device_budget)
+                and self.emitter is None)
+
+    def _budgeted(self):
+        return self.device_budget and self.max_incremental_percent < 100.0
 
     def _fused_available(self):
         return self._fused_configured() and getattr(self, "have_frame", False)
 
-    def correlated_update_fused(self):
+    def correlated_update_fused(self, pending=False):
         """The same evaluation with the count kept on the device: importance + threshold + tile lists in one launch, the lists
         lined up by a second, the tracer and the - old / + new splat launched over the budget and bounded by the device count.
-        The host reads the count once, after everything is enqueued (from the selection's mailbox).  Returns n re-traced."""
+        The host reads the count once, after everything is enqueued (from the selection's mailbox).  Returns n re-traced.
+        With a device budget below 100 % the selection is cut to the budget's most important photons before the trace;
+        pending: a continuation -- no importance pass, the photons whose key is still below 0x7fffffff are the candidates."""
         ctx, torch = self.ctx, self.torch
         n_total = self.n
         if self.selection is None:
@@ -601,13 +624,29 @@ class CorrelatedPhotonMapper(PhotonFrame):
         if getattr(self, "_occupancy_bits", None) is not None:   # (the bits of the grid's last importance_tf launch)
             sel.set_occupancy(self.importance_grid, self._occupancy_bits)
         self.params.flags = 0                            # correlated: RNG state is NOT written back
-        if self.retrace_in_importance_pass:
+        budget = ctx.update_budget(n_total, self.max_incremental_percent) if self._budgeted() else None
+        if budget is not None:
+            if pending:
+                sel.select_pending(self.importance, 0, n_total)
+            elif self.detector == "equal":
+                sel.photon_importance_equal(0, n_total, self.equal_percentage, self._equal_iteration, self.importance)
+                self._equal_iteration += 1
+            else:
+                sel.photon_importance(self.importance_grid, self.brick_dims, (float(self.region),) * 3, list(self.vol.desc.texture_to_index),
+                                      self.photons, 0, self.light_samples, self.isect, n_total, self.I, n_total, self.importance,
+                                      fix_exit_point=self.fix_exit_point)
+            sel.finish(self.indices, budget=budget, importances=self.importance)
+            if budget > 0:
+                ctx.trace_selected(self.vol, self.tf, self.aabb, self.params, self.light_samples, self.isect, self.indices, sel, budget,
+                                   self.rng, self.photons, old_photons=self.old_photons, reset_importances=self.importance)
+            old_stride = n_indices = budget
+        elif self.retrace_in_importance_pass:
             # detector + threshold + tracer in one launch; the replaced records stay at the photons' own indices
             sel.photon_importance_retrace(self.importance_grid, self.brick_dims, (float(self.region),) * 3, list(self.vol.desc.texture_to_index),
                                           self.vol, self.tf, self.aabb, self.params, self.light_samples, self.isect, self.importance,
                                           self.rng, self.photons, self.old_photons, fix_exit_point=self.fix_exit_point)
             sel.finish(self.indices)
-            old_stride = 0
+            old_stride, n_indices = 0, n_total
         else:
             sel.photon_importance(self.importance_grid, self.brick_dims, (float(self.region),) * 3, list(self.vol.desc.texture_to_index),
                                   self.photons, 0, self.light_samples, self.isect, n_total, self.I, n_total, self.importance,
@@ -615,15 +654,18 @@ class CorrelatedPhotonMapper(PhotonFrame):
             sel.finish(self.indices)
             ctx.trace_selected(self.vol, self.tf, self.aabb, self.params, self.light_samples, self.isect, self.indices, sel, n_total,
                                self.rng, self.photons, old_photons=self.old_photons, reset_importances=self.importance)
-            old_stride = n_total
+            old_stride = n_indices = n_total
         max_recomp = int(self.n * (self.incremental_threshold_percent / 100.0))
         if self.touched_mask is not None:
             self.touched_mask.zero_()
-        ctx.splat_delta(self.old_photons, old_stride, self.photons, self.indices, sel, n_total, self.grid, self.radius, self.scale,
+        ctx.splat_delta(self.old_photons, old_stride, self.photons, self.indices, sel, n_indices, self.grid, self.radius, self.scale,
                         self.n, self.I, self.light_volume, apply_below=max(max_recomp, 1), brick_mask=self.touched_mask)
-        n = sel.count()                                  # the one host read, behind everything enqueued
+        n, n_changed = sel.counts()                      # the one host read, behind everything enqueued
         self.n_recomputed = n
-        self.remaining, self.remaining_offset = 0, n
+        self.n_changed_last = n_changed
+        self.remaining, self.remaining_offset = n_changed - n, n   # (the budget's rest is pending: its keys say which)
+        if budget == 0:                                  # a budget of no photon at all would leave them pending for ever
+            self.remaining = 0
         if n == 0:
             self.last_path = "unchanged"
         elif n < max_recomp:
@@ -668,6 +710,8 @@ class CorrelatedPhotonMapper(PhotonFrame):
         """Progressive continuation on the 100 ms timer (tracercl.cpp:387-419,534-540)."""
         if self.remaining <= 0:
             return 0
+        if self._budgeted() and self._fused_available():
+            return self.correlated_update_fused(pending=True)
         return self._retrace_batch()
 
     def _retrace_batch(self, ranked=True):

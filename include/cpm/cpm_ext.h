@@ -253,8 +253,9 @@ int cpm_importance_tf_occupancy(cpm_ctx* ctx, const uint16_t* minmax2, const uin
  *
  * Results are those of cpm_photon_importance + cpm_select_changed + cpm_trace + cpm_reset_importance +
  * cpm_splat_selected(-1, snapshot) + cpm_splat_selected(+1) bit for bit (the splat sums within atomic-order tolerance).
- * It covers the case in which every changed photon is traced in this evaluation (maxIncrementalPhotonsToUpdate = 100 %,
- * the default); a smaller budget needs the ranking by importance and takes cpm_select_recompute with its host decision. */
+ * That chain traces every changed photon in this evaluation (maxIncrementalPhotonsToUpdate = 100 %, the default).  A smaller
+ * budget takes cpm_selection_finish_budget in place of cpm_selection_finish (below: the budgeted update): the ranking by
+ * importance as a selection by rank on the device, still without a host decision. */
 
 typedef struct cpm_selection cpm_selection;
 
@@ -324,6 +325,46 @@ const int32_t* cpm_selection_count_device(const cpm_selection* sel);
  * memory; later work in the stream keeps running), not for the stream.  Replaces the blocking wait on the reduce's
  * read-back (ref processor/progressivephotontracercl.cpp:343-345,374). */
 int cpm_selection_count(cpm_ctx* ctx, cpm_selection* sel, int32_t* n_out);
+
+/* ---- the budgeted update: the n most important changed photons, chosen on the device
+ *
+ * An evaluation re-traces at most budget = maxIncrementalPhotonsToUpdate per cent of the photons, the most important first, and
+ * a timer continues with the rest (ref processor/progressivephotontracercl.cpp:83,358-419,534-540).  With K[i] photon i's key
+ * after the importance pass (smaller = more important, 0x7fffffff = unchanged), C = { i : K[i] < 0x7fffffff } and
+ * m = min(|C|, budget), the photons chosen are the first m of C ordered by (K[i], i): the first m entries of
+ * cpm_select_recompute's stable sort -- what the reference traces -- listed in ascending index order (what cpm_sort_keys makes of
+ * that batch).  Ties on the cut go to the lower index.  The keys are NOT permuted: after cpm_trace_selected with
+ * reset_importances the chosen photons' keys are back at 0x7fffffff, every other key is untouched, and what is still pending
+ * is whatever is still below 0x7fffffff -- choosing `budget` of it again and again walks the one stable sort slice by slice.
+ *
+ * One budgeted evaluation (cpm_photon_importance_retrace[_lights] cannot serve it: the choice must precede the trace):
+ *   cpm_selection_begin
+ *   cpm_photon_importance_select / cpm_photon_importance_equal_select   (per light; a continuation: cpm_selection_select_pending)
+ *   cpm_selection_finish_budget(budget)
+ *   cpm_trace_selected   (per light)   max_indices = budget, old_photons8, reset_importances
+ *   cpm_splat_delta                    old_stride = budget
+ * A launch count that depends on neither the photons nor the changed ones, only integer atomics (the list and the counts do not
+ * depend on their order: bit-reproducible), work over the tiles' lists only, no host read. */
+
+/* (int)((percent / 100.f) * (float)n_photons): the reference's float arithmetic (ref processor/progressivephotontracercl.cpp:387-388);
+ * host only.  0 for a percentage that is not positive. */
+int32_t cpm_update_budget(size_t n_photons, float percent);
+/* A continuation's selection: the photons of one light whose key is < 0x7fffffff are listed per tile, from the keys as they are --
+ * the tile lists cpm_photon_importance_select leaves, without an importance pass and without writing a key. */
+int cpm_selection_select_pending(cpm_ctx* ctx, cpm_selection* sel, const uint32_t* importances, int photon_offset,
+                                 int n_light_samples, cpm_stream stream);
+/* In place of cpm_selection_finish.  importances: the key buffer the selection's select calls worked on.  indices_out[0 .. m) as
+ * above (room for min(budget, photons the select calls spanned) entries; the rest is not written); m -> cpm_selection_count_device,
+ * m and |C| -> the mailbox (cpm_selection_counts; cpm_selection_count gives m).  budget >= |C|: cpm_selection_finish's list and
+ * count, bit for bit -- the device takes that way itself, the host neither knows nor needs to.  budget == 0 selects nothing.  A
+ * selection one of whose select calls failed publishes 0 / 0 and reports it, as cpm_selection_finish does.
+ * Replaces sortIndicesByImportance, the host's min(count, budget) behind its read-back and the keys-only sort of the batch
+ * (ref processor/progressivephotontracercl.cpp:358-419,467-473). */
+int cpm_selection_finish_budget(cpm_ctx* ctx, cpm_selection* sel, const uint32_t* importances, int32_t budget,
+                                uint32_t* indices_out, cpm_stream stream);
+/* m (photons listed) and |C| (photons changed / pending) of the last finish of either kind, from the mailbox: a poll of pinned
+ * memory, no stream wait.  After cpm_selection_finish both are its count. */
+int cpm_selection_counts(cpm_ctx* ctx, cpm_selection* sel, int32_t* n_selected, int32_t* n_changed);
 
 /* cpm_trace's recompute variant with the number of indices read on the device: thread j < min(*n_indices_dev, max_indices)
  * traces light sample indices[j] - photon_offset (threads whose index falls outside this light's range do nothing, as in
