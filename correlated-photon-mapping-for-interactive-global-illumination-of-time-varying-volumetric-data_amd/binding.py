@@ -55,7 +55,8 @@ EXT_SYMBOLS = [
     "cpm_bricklist_segment_bytes", "cpm_reduce_grid_bricklists", "cpm_bricklist_reduce_complete", "cpm_bricklist_reduce_open", "cpm_bricklist_pack_grid",
     "cpm_bricklist_reduce_exchange", "cpm_gather_fast_segment", "cpm_bricklist_segment_to_grid", "cpm_comm_send", "cpm_comm_recv",
     "cpm_light_volume_texels", "cpm_gl_available", "cpm_gl_register_buffer", "cpm_gl_acquire", "cpm_gl_release", "cpm_gl_buffer_pointer",
-    "cpm_gl_copy_to_buffer", "cpm_gl_unregister", "cpm_render"
+    "cpm_gl_copy_to_buffer", "cpm_gl_unregister", "cpm_render", "cpm_render_accel_create", "cpm_render_accel_destroy",
+    "cpm_render_accel_update", "cpm_render_accel_info", "cpm_render_ex"
 ]
 ABI_SYMBOLS = CORE_SYMBOLS + EXT_SYMBOLS
 CPM_GL_TEXEL_F32, CPM_GL_TEXEL_F16 = 0, 1
@@ -137,6 +138,11 @@ class RenderDesc(C.Structure):
     nullable entry / exit device buffers."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ndc_to_texture", C.c_float * 16), ("sampling_rate", C.c_float),
                 ("colored_light", C.c_int32), ("entry", C.c_void_p), ("exit", C.c_void_p)]
+
+
+class RenderOptions(C.Structure):
+    """cpm_render_options (include/cpm/cpm_ext.h): nullable accel, host clip box (8 floats), device stats (2 x uint32)."""
+    _fields_ = [("accel", C.c_void_p), ("clip_aabb", C.POINTER(C.c_float)), ("stats", C.c_void_p)]
 
 
 def camera_ndc_to_texture(look_from, look_to, look_up, fov_deg, aspect, near, far, texture_to_world=None):
@@ -401,6 +407,12 @@ def load_library() -> C.CDLL:
         "cpm_gl_copy_to_buffer": (i32, [vp, vp, sz, i32, vp, vp]),
         "cpm_render": (i32, [vp, vp, vp, vp, P(GridDesc), P(RenderDesc), vp, vp]),
         "cpm_gl_unregister": (None, [vp, vp]),
+        "cpm_render_accel_create": (i32, [vp, P(VolumeDesc), i32, P(vp)]),
+        "cpm_render_accel_destroy": (None, [vp, vp]),
+        "cpm_render_accel_update": (i32, [vp, vp, vp, vp, vp]),
+        "cpm_render_accel_info": (i32, [vp, vp, P(C.c_int32 * 3), P(u32), vp]),
+        "cpm_render_ex": (i32, [vp, vp, vp, vp, P(GridDesc), P(RenderDesc), P(RenderOptions), vp, vp]),
+        "cpm_debug_set_render_bits_lds": (None, [vp, i32]),
         "cpm_volume_device_data": (vp, [vp, P(sz)]),
         "cpm_volume_download": (i32, [vp, vp, vp, vp]),
         # include/cpm/cpm_profile.h (measurement hooks)
@@ -839,12 +851,23 @@ class Context:
         self._check(self.lib.cpm_light_volume_texels(self.h, self._ptr(light_volume), light_volume.numel(), int(texel), self._ptr(out), self._stream()))
 
     # -- raycaster
+    def render_accel(self, vol, brick: int = 8):
+        """cpm_render_accel for volumes of vol's dims and voxel type: the raycaster's skip structure (bricks of 4, 8 or 16 voxels).  Call
+        .update(vol, tf) before the first render with it, and after every change of the voxels or of the TF."""
+        h = C.c_void_p()
+        self._check(self.lib.cpm_render_accel_create(self.h, C.byref(vol.desc), int(brick), C.byref(h)))
+        return RenderAccel(self, h, int(brick))
+
     def render(self, vol, tf, light_volume, grid: GridDesc, width, height, *, ndc_to_texture=None, entry=None, exit=None,
-               sampling_rate=1.0, colored_light=True, out=None):
+               sampling_rate=1.0, colored_light=True, out=None, accel=None, clip=None, stats=None):
         """cpm_render: the volume classified by `tf` and lit by `light_volume` (a float32 device tensor of cells * grid.channels,
         as the gather writes it) -> (height, width, 4) float32 premultiplied RGBA, row 0 = the bottom row.  Rays from the camera
         (ndc_to_texture: 16 floats, column-major, e.g. camera_ndc_to_texture) or from entry / exit device tensors of
-        (height, width, 4) float32 in texture space (then the matrix is ignored)."""
+        (height, width, 4) float32 in texture space (then the matrix is ignored).
+
+        accel (a RenderAccel, updated for this vol and tf), clip (8 floats: min.xyz, 1, max.xyz, 1 in texture space, the tracer's aabb)
+        or stats (a device tensor of 2 x int32 / uint32 words the launch ADDS its evaluated / skipped sample counts to) route the call
+        to cpm_render_ex; with none of them it is cpm_render."""
         import numpy as np
         if (entry is None) != (exit is None):
             raise ValueError("entry and exit are given together")
@@ -867,8 +890,25 @@ class Context:
         d.exit = None if exit is None else self._ptr(exit, f32).value
         if out is None:
             out = self.torch.empty((max(int(height), 0), max(int(width), 0), 4), dtype=f32, device=self.device)
-        self._check(self.lib.cpm_render(self.h, vol.h, tf.h, self._ptr(light_volume, f32), C.byref(grid), C.byref(d), self._ptr(out, f32),
-                                        self._stream()))
+        if accel is None and clip is None and stats is None:
+            self._check(self.lib.cpm_render(self.h, vol.h, tf.h, self._ptr(light_volume, f32), C.byref(grid), C.byref(d), self._ptr(out, f32),
+                                            self._stream()))
+            return out
+        o = RenderOptions()
+        if accel is not None:
+            if accel.stale(vol, tf):
+                raise ValueError("render: the accel has not seen this volume and TF as they are now -- call accel.update(vol, tf) first")
+            o.accel = accel.h.value
+        box = None
+        if clip is not None:
+            box = (C.c_float * 8)(*np.asarray(clip, np.float32).reshape(8).tolist())
+            o.clip_aabb = C.cast(box, C.POINTER(C.c_float))
+        if stats is not None:
+            if stats.numel() != 2 or stats.element_size() != 4:
+                raise ValueError("stats must hold 2 x 32-bit words")
+            o.stats = self._ptr(stats).value
+        self._check(self.lib.cpm_render_ex(self.h, vol.h, tf.h, self._ptr(light_volume, f32), C.byref(grid), C.byref(d), C.byref(o),
+                                           self._ptr(out, f32), self._stream()))   # (the call has consumed the clip box on return)
         return out
 
     # -- temporal interpolation
@@ -881,6 +921,7 @@ class Context:
 
     def volume_mix(self, v0, v1, weight, out):
         self._check(self.lib.cpm_volume_mix(self.h, v0.h, v1.h, float(weight), out.h, self._stream()))
+        out.version += 1
 
     # -- correlated
     def volume_minmax(self, vol, region, out):
@@ -1169,10 +1210,66 @@ class Comm:
             pass
 
 
+class RenderAccel:
+    """cpm_render_accel: per-brick value ranges of a volume and the bricks a TF leaves empty (Context.render_accel).  The library remembers
+    which volume and TF objects the accel saw; this object also remembers their `version` counters, so that a write made through the
+    binding (Volume.update, Context.volume_mix, TransferFunction.update) or a volume handed out anew (VolumeStream.acquire) is noticed."""
+
+    def __init__(self, ctx, h, brick):
+        self.ctx, self.h, self.brick = ctx, h, brick
+        self._vol = self._tf = None
+        self._vol_version = self._tf_version = -1
+
+    def _vol_stale(self, vol):
+        return vol is not self._vol or vol.version != self._vol_version
+
+    def _tf_stale(self, tf):
+        return tf is not self._tf or tf.version != self._tf_version
+
+    def stale(self, vol, tf):
+        return self._vol_stale(vol) or self._tf_stale(tf)
+
+    def update(self, vol=None, tf=None):
+        """Rebuild the range grid from `vol` and / or the TF's part from `tf` (None: unchanged), then the empty bits."""
+        self.ctx._check(self.ctx.lib.cpm_render_accel_update(self.ctx.h, self.h, vol.h if vol is not None else None,
+                                                             tf.h if tf is not None else None, self.ctx._stream()))
+        if vol is not None:
+            self._vol, self._vol_version = vol, vol.version
+        if tf is not None:
+            self._tf, self._tf_version = tf, tf.version
+
+    def refresh(self, vol, tf):
+        """update() with whichever of the two this accel has not seen as it is now; -> (volume rebuilt, TF rebuilt)."""
+        v, t = self._vol_stale(vol), self._tf_stale(tf)
+        if v or t:
+            self.update(vol if v else None, tf if t else None)
+        return v, t
+
+    def info(self):
+        """((bricks along x, y, z), number of empty bricks) -- synchronises."""
+        nb, n = (C.c_int32 * 3)(), C.c_uint32()
+        self.ctx._check(self.ctx.lib.cpm_render_accel_info(self.ctx.h, self.h, C.byref(nb), C.byref(n), self.ctx._stream()))
+        return tuple(nb), n.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.cpm_render_accel_destroy(self.ctx.h, self.h)
+            self.h = None
+        self._vol = self._tf = None
+
+    def __del__(self):
+        try:
+            if self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
 class Volume:
     def __init__(self, ctx: Context, h, desc: VolumeDesc, owned: bool = True):
         """owned=False: a volume something else destroys (a cpm_volume_stream's slot)."""
         self.ctx, self.h, self.desc, self.owned = ctx, h, desc, owned
+        self.version = 0   # counts the writes to the voxels made through this object (what a RenderAccel compares)
 
     @property
     def dims(self):
@@ -1186,6 +1283,7 @@ class Volume:
         else:
             ptr, is_dev = self.ctx._ptr(voxels), 1
         self.ctx._check(self.ctx.lib.cpm_volume_update(self.ctx.h, self.h, ptr, is_dev, self.ctx._stream()))
+        self.version += 1
 
     def download(self):
         """Voxels as a numpy array [z, y, x] (blocking device -> host copy)."""
@@ -1366,6 +1464,7 @@ class VolumeStream:
 class TransferFunction:
     def __init__(self, ctx: Context, h, width):
         self.ctx, self.h, self.width = ctx, h, width
+        self.version = 0   # counts the updates (what a RenderAccel compares)
 
     def update(self, rgba):
         import numpy as np
@@ -1375,6 +1474,7 @@ class TransferFunction:
         else:
             ptr, is_dev = self.ctx._ptr(rgba), 1
         self.ctx._check(self.ctx.lib.cpm_tf_update(self.ctx.h, self.h, ptr, is_dev, self.ctx._stream()))
+        self.version += 1
 
     def __del__(self):
         try:

@@ -46,6 +46,7 @@ struct cpm_ctx {
         int brick_streaming = 1, select_partition = 1;
         int stream_wg_per_cu = -1;
         int fail_next_select = 0;
+        int render_bits_lds = 4096;   // cpm_render_ex: empty bits up to this many bytes are staged into LDS, larger sets are read through L2
     } dbg;
     struct cpm_trace_order* trace_order = nullptr;  // cpm_trace_set_order (not owned)
     bool trace_order_measure = false;               // ... and whether the launches add their costs to it

@@ -15,6 +15,18 @@
 //   * the light volume (8 loads of 4 B, or 8 of 16 B for 4 channels) is fetched only behind c.a > 0, so empty space costs the
 //     volume and TF fetches alone.
 //   * no atomics, no global writes but the one float4 pixel store: the image is deterministic by construction.
+//
+// cpm_render_ex adds, as instantiations of their own (render_ex_kernel; render_kernel compiles as it did without them):
+//   * R_SKIP: empty-space skipping over a cpm_render_accel.  A sample whose footprint is based in a brick whose bit is set has alpha 0
+//     (cpm_render_accel.hip), and a sample with alpha 0 changes no state, so the loop may jump k over a run of such samples.  The brick
+//     comes from the sampler's own coord() floors; how far to jump is a guess from the ray's exit out of the brick, and the guess is
+//     VERIFIED: a sample's floors are weakly monotone in k along every axis (k -> t -> p -> floor are all monotone roundings), so if
+//     sample k and sample k + j are based in the same brick, so is every sample between them.  A wrong guess costs a short jump, never
+//     a wrong pixel.  The bits sit in LDS behind the TF column when they are small (4 KiB for 32^3 bricks), else they are read through
+//     L2; one word per sample.
+//   * R_STATS: samples evaluated / skipped, summed over the wave and added with one atomic per counter and wave.
+//   * the clip box: the slab test against (lo, hi) from the arguments instead of (0, 1).
+#include "cpm_render_accel.h"
 #include "cpm_trace_body.hip.h"
 
 using namespace cpm;
@@ -94,27 +106,57 @@ CPM_DEV void unproject(const float* m, float x, float y, float z, float& px, flo
     pz = (m[2] * x + m[6] * y + m[10] * z + m[14]) / w;
 }
 
-CPM_DEV void slab(float o, float d, float& s0, float& s1) {
+CPM_DEV void slab(float o, float d, float lo, float hi, float& s0, float& s1) {
     const float inv = 1.0f / d;
     // d = 0: +-inf outside the slab, [-inf, inf] inside it; o on a face gives 0 * inf = NaN for that face, which fminf / fmaxf drop,
     // so the other face's infinity empties the range -- a ray in the plane of a face is a miss
-    const float ta = (0.0f - o) * inv, tb = (1.0f - o) * inv;
+    const float ta = (lo - o) * inv, tb = (hi - o) * inv;
     s0 = max_(s0, min_(ta, tb));
     s1 = min_(s1, max_(ta, tb));
 }
 
-template <int DT, int CH>
-__global__ __launch_bounds__(256) void render_kernel(const RenderArgs A) {
-    extern __shared__ float4 lut[];
-    for (int i = threadIdx.x; i < A.tf_width; i += 256) lut[i] = A.tf[i];
-    __syncthreads();
+enum { R_SKIP = 1, R_STATS = 2, R_EX = 4 };
 
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int pi = blockIdx.x * 16 + (w & 1) * 8 + (lane & 7);
-    const int pj = blockIdx.y * 16 + (w >> 1) * 8 + (lane >> 3);
-    if (pi >= A.width || pj >= A.height) return;
-    const int pix = pj * A.width + pi;
+// what cpm_render_ex adds to a launch
+struct RenderExArgs {
+    float clip_lo[3], clip_hi[3];
+    const uint32_t* bits;             // cpm_render_accel::bits (1 = empty); R_SKIP only
+    uint32_t bits_words;              // words staged into LDS behind the TF column; 0: read them from `bits`
+    int lg, nbx, nbxy;                // log2(brick), bricks along x, bricks per z slab
+    float last_bx, last_by, last_bz;  // the last brick a footprint can be based in along each axis: max(dim - 2, 0) >> lg
+    uint32_t* stats;                  // R_STATS only
+};
 
+CPM_DEV void sample_position(const float ex, const float ey, const float ez, const float dirx, const float diry, const float dirz,
+                             const float tIncr, const int k, float& px, float& py, float& pz) {
+    const float t = ((float)k + 0.5f) * tIncr;
+    px = ex + t * dirx; py = ey + t * diry; pz = ez + t * dirz;
+}
+
+// the brick a sample at p is based in: the floors of sample_volume's own coord() calls, shifted
+CPM_DEV int sample_brick(const VolDev& V, const RenderExArgs& X, float px, float py, float pz, int& ix, int& iy, int& iz) {
+    float flx, fly, flz, a;
+    coord(px, V.fx, V.mx1, V.mx2, flx, a);
+    coord(py, V.fy, V.my1, V.my2, fly, a);
+    coord(pz, V.fz, V.mz1, V.mz2, flz, a);
+    ix = (int)flx; iy = (int)fly; iz = (int)flz;
+    return (ix >> X.lg) + X.nbx * (iy >> X.lg) + X.nbxy * (iz >> X.lg);
+}
+
+// along one axis: the (real-valued) sample index at which u = p * dim - 1/2 leaves the brick [b << lg, (b + 1) << lg); the first and the
+// last brick reach to infinity (coord() clamps).  A guess: rounded any way, v_rcp_f32.
+CPM_DEV float brick_exit(float e, float step, float dimf, int i, int lg, float last) {
+    const int b = i >> lg;
+    const float su = step * dimf;                       // voxels per sample
+    const float u0 = fma_(e, dimf, fma_(0.5f, su, -0.5f));  // u of sample 0
+    const float inf = __builtin_inff();
+    const float bound = su > 0.0f ? ((float)b < last ? (float)((b + 1) << lg) : inf) : (b > 0 ? (float)(b << lg) : -inf);
+    return su == 0.0f ? inf : (bound - u0) * __builtin_amdgcn_rcpf(su);
+}
+
+template <int DT, int CH, int MODE>
+CPM_DEV float4 render_pixel(const RenderArgs& A, const RenderExArgs& X, const float4* lut, const uint32_t* lbits, const int pi, const int pj,
+                            const int pix, uint32_t& evaluated, uint32_t& skipped) {
     float ex, ey, ez, rx, ry, rz;
     bool hit;
     if (A.entry) {
@@ -130,9 +172,15 @@ __global__ __launch_bounds__(256) void render_kernel(const RenderArgs A) {
         unproject(A.m, nx, ny, 1.0f, fx, fy, fz);
         const float dx = fx - ox, dy = fy - oy, dz = fz - oz;
         float s0 = 0.0f, s1 = 1.0f;
-        slab(ox, dx, s0, s1);
-        slab(oy, dy, s0, s1);
-        slab(oz, dz, s0, s1);
+        if (MODE & R_EX) {
+            slab(ox, dx, X.clip_lo[0], X.clip_hi[0], s0, s1);
+            slab(oy, dy, X.clip_lo[1], X.clip_hi[1], s0, s1);
+            slab(oz, dz, X.clip_lo[2], X.clip_hi[2], s0, s1);
+        } else {
+            slab(ox, dx, 0.0f, 1.0f, s0, s1);
+            slab(oy, dy, 0.0f, 1.0f, s0, s1);
+            slab(oz, dz, 0.0f, 1.0f, s0, s1);
+        }
         hit = s0 < s1;
         ex = ox + s0 * dx; ey = oy + s0 * dy; ez = oz + s0 * dz;
         rx = (ox + s1 * dx) - ex; ry = (oy + s1 * dy) - ey; rz = (oz + s1 * dz) - ez;
@@ -147,8 +195,31 @@ __global__ __launch_bounds__(256) void render_kernel(const RenderArgs A) {
         const float dirx = rx / tEnd, diry = ry / tEnd, dirz = rz / tEnd;
         const float expo = tIncr * kRefSamplingInterval;
         for (int k = 0; k < n; ++k) {
-            const float t = ((float)k + 0.5f) * tIncr;
-            const float px = ex + t * dirx, py = ey + t * diry, pz = ez + t * dirz;
+            float px, py, pz;
+            sample_position(ex, ey, ez, dirx, diry, dirz, tIncr, k, px, py, pz);
+            if (MODE & R_SKIP) {
+                int ix, iy, iz;
+                const int b = sample_brick(A.vol, X, px, py, pz, ix, iy, iz);
+                const uint32_t word = X.bits_words ? lbits[b >> 5] : X.bits[b >> 5];
+                if ((word >> (b & 31)) & 1u) {
+                    // every sample up to `last` is skipped: the guess, then the proof (the header comment) -- or this sample alone
+                    const float kx = brick_exit(ex, tIncr * dirx, A.vol.fx, ix, X.lg, X.last_bx);
+                    const float ky = brick_exit(ey, tIncr * diry, A.vol.fy, iy, X.lg, X.last_by);
+                    const float kz = brick_exit(ez, tIncr * dirz, A.vol.fz, iz, X.lg, X.last_bz);
+                    const float kf = __builtin_floorf(min_(min_(kx, ky), kz) - 0.0625f);
+                    int last = (int)max_(min_(kf, (float)(n - 1)), (float)k);  // (fminf / fmaxf drop a NaN guess)
+                    if (last > k) {
+                        float qx, qy, qz;
+                        int jx, jy, jz;
+                        sample_position(ex, ey, ez, dirx, diry, dirz, tIncr, last, qx, qy, qz);
+                        if (sample_brick(A.vol, X, qx, qy, qz, jx, jy, jz) != b) last = k;
+                    }
+                    if (MODE & R_STATS) skipped += (uint32_t)(last - k + 1);
+                    k = last;
+                    continue;
+                }
+            }
+            if (MODE & R_STATS) ++evaluated;
             const float v = sample_volume<DT>(A.vol, px, py, pz);
             float fl, a;
             coord(v, A.tf_wf, A.tf_m1, A.tf_m2, fl, a);
@@ -170,16 +241,60 @@ __global__ __launch_bounds__(256) void render_kernel(const RenderArgs A) {
             }
         }
     }
-    A.out[pix] = res;
+    return res;
+}
+
+template <int DT, int CH>
+__global__ __launch_bounds__(256) void render_kernel(const RenderArgs A) {
+    extern __shared__ float4 lut[];
+    for (int i = threadIdx.x; i < A.tf_width; i += 256) lut[i] = A.tf[i];
+    __syncthreads();
+
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pi = blockIdx.x * 16 + (w & 1) * 8 + (lane & 7);
+    const int pj = blockIdx.y * 16 + (w >> 1) * 8 + (lane >> 3);
+    if (pi >= A.width || pj >= A.height) return;
+    const int pix = pj * A.width + pi;
+    uint32_t evaluated = 0, skipped = 0;
+    const RenderExArgs X{};
+    A.out[pix] = render_pixel<DT, CH, 0>(A, X, lut, nullptr, pi, pj, pix, evaluated, skipped);
+}
+
+template <int DT, int CH, int MODE>
+__global__ __launch_bounds__(256) void render_ex_kernel(const RenderArgs A, const RenderExArgs X) {
+    extern __shared__ float4 lut[];
+    uint32_t* lbits = reinterpret_cast<uint32_t*>(lut + A.tf_width);
+    for (int i = threadIdx.x; i < A.tf_width; i += 256) lut[i] = A.tf[i];
+    if (MODE & R_SKIP)
+        for (uint32_t i = threadIdx.x; i < X.bits_words; i += 256) lbits[i] = X.bits[i];
+    __syncthreads();
+
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pi = blockIdx.x * 16 + (w & 1) * 8 + (lane & 7);
+    const int pj = blockIdx.y * 16 + (w >> 1) * 8 + (lane >> 3);
+    uint32_t evaluated = 0, skipped = 0;
+    if (pi < A.width && pj < A.height) {
+        const int pix = pj * A.width + pi;
+        A.out[pix] = render_pixel<DT, CH, MODE>(A, X, lut, lbits, pi, pj, pix, evaluated, skipped);
+    }
+    if (MODE & R_STATS) {  // all 64 lanes are here again: the wave's sums, one atomic each
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            evaluated += (uint32_t)__shfl_xor((int)evaluated, m);
+            skipped += (uint32_t)__shfl_xor((int)skipped, m);
+        }
+        if (lane == 0) {
+            atomicAdd(&X.stats[0], evaluated);
+            if (MODE & R_SKIP) atomicAdd(&X.stats[1], skipped);
+        }
+    }
 }
 
 }  // namespace
 
-extern "C" {
-
-int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
-               const cpm_render_desc* desc, float* rgba_out, cpm_stream stream) {
-    CPM_ENTER(ctx);
+// validation and kernel arguments shared by cpm_render and cpm_render_ex; lds = the TF column's bytes
+static int render_prepare(cpm_ctx* ctx, const char* who, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+                          const cpm_render_desc* desc, float* rgba_out, RenderArgs& A, size_t& lds) {
     CPM_REQUIRE(ctx, vol && tf && light_volume && grid && desc && rgba_out, "cpm_render: null argument");
     const cpm_render_desc& D = *desc;
     CPM_REQUIRE(ctx, grid->channels == 1 || grid->channels == 4, "cpm_render: light volume channels must be 1 or 4");
@@ -195,18 +310,9 @@ int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const floa
     if (D.entry) { CPM_REQUIRE_ALIGNED16(ctx, D.entry, "cpm_render"); CPM_REQUIRE_ALIGNED16(ctx, D.exit, "cpm_render"); }
     const cpm_volume_desc& vd = vol->desc;
     CPM_REQUIRE(ctx, (unsigned long long)vd.dims[0] * vd.dims[1] * vd.dims[2] < (1ull << 32), "cpm_render: volume too large");
-    const size_t lds = (size_t)tf->width * sizeof(float4);
-    if (lds > ctx->lds_per_block) return set_error(ctx, CPM_ERR_UNSUPPORTED, "cpm_render", "the TF's RGBA column does not fit the workgroup's LDS");
+    lds = (size_t)tf->width * sizeof(float4);
+    if (lds > ctx->lds_per_block) return set_error(ctx, CPM_ERR_UNSUPPORTED, who, "the TF's RGBA column does not fit the workgroup's LDS");
 
-    hipStream_t s = (hipStream_t)stream;
-    tracer::TraceArgs T{};
-    make_vol_dev(vol, T.vol);
-    bool linear = false;
-    const int rc = trace_volume_source(ctx, vol, false, s, T, &linear);  // a stale footprint copy (cpm_volume_mix) is rebuilt first
-    if (rc) return rc;
-
-    RenderArgs A{};
-    A.vol = T.vol;
     A.tf = reinterpret_cast<const float4*>(tf->rgba);
     A.tf_width = tf->width;
     A.tf_wf = (float)tf->width; A.tf_m1 = (float)(tf->width - 1); A.tf_m2 = (float)(tf->width - 2);
@@ -225,14 +331,40 @@ int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const floa
     A.entry = reinterpret_cast<const float4*>(D.entry);
     A.exit = reinterpret_cast<const float4*>(D.exit);
     A.out = reinterpret_cast<float4*>(rgba_out);
+    return CPM_OK;
+}
 
-    const dim3 g(div_up(D.width, 16), div_up(D.height, 16)), b(256);
+// the tracer's view of the volume; a stale footprint copy (cpm_volume_mix) is rebuilt first
+static int render_volume(cpm_ctx* ctx, const cpm_volume* vol, hipStream_t s, RenderArgs& A) {
+    tracer::TraceArgs T{};
+    make_vol_dev(vol, T.vol);
+    bool linear = false;
+    const int rc = trace_volume_source(ctx, vol, false, s, T, &linear);
+    if (rc) return rc;
+    A.vol = T.vol;
+    return CPM_OK;
+}
+
+extern "C" {
+
+int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+               const cpm_render_desc* desc, float* rgba_out, cpm_stream stream) {
+    CPM_ENTER(ctx);
+    RenderArgs A{};
+    size_t lds = 0;
+    int rc = render_prepare(ctx, "cpm_render", vol, tf, light_volume, grid, desc, rgba_out, A, lds);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = render_volume(ctx, vol, s, A);
+    if (rc) return rc;
+
+    const dim3 g(div_up(A.width, 16), div_up(A.height, 16)), b(256);
 #define CPM_RENDER_LAUNCH(DT)                                                                               \
     do {                                                                                                    \
         if (grid->channels == 1) CPM_LAUNCH(ctx, (render_kernel<DT, 1>), g, b, lds, s, A);                  \
         else CPM_LAUNCH(ctx, (render_kernel<DT, 4>), g, b, lds, s, A);                                      \
     } while (0)
-    switch (vd.dtype) {
+    switch (vol->desc.dtype) {
         case CPM_U8: CPM_RENDER_LAUNCH(CPM_U8); break;
         case CPM_U16: CPM_RENDER_LAUNCH(CPM_U16); break;
         case CPM_F16: CPM_RENDER_LAUNCH(CPM_F16); break;
@@ -240,6 +372,81 @@ int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const floa
     }
 #undef CPM_RENDER_LAUNCH
     CPM_LAUNCH_CHECK(ctx, "render_kernel");
+    return CPM_OK;
+}
+
+void cpm_debug_set_render_bits_lds(cpm_ctx* ctx, int max_bytes) { if (ctx) ctx->dbg.render_bits_lds = max_bytes; }
+
+int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+                  const cpm_render_desc* desc, const cpm_render_options* options, float* rgba_out, cpm_stream stream) {
+    CPM_ENTER(ctx);
+    RenderArgs A{};
+    size_t lds = 0;
+    int rc = render_prepare(ctx, "cpm_render_ex", vol, tf, light_volume, grid, desc, rgba_out, A, lds);
+    if (rc) return rc;
+    const cpm_render_accel* accel = options ? options->accel : nullptr;
+    const float* clip = options ? options->clip_aabb : nullptr;
+    uint32_t* stats = options ? options->stats : nullptr;
+    RenderExArgs X{};
+    for (int a = 0; a < 3; ++a) { X.clip_lo[a] = 0.0f; X.clip_hi[a] = 1.0f; }
+    if (clip) {
+        for (int a = 0; a < 3; ++a) {
+            const float lo = clip[a], hi = clip[4 + a];
+            CPM_REQUIRE(ctx, lo - lo == 0.0f && hi - hi == 0.0f && lo < hi, "cpm_render_ex: the clip box must be finite with min < max on every axis");
+            X.clip_lo[a] = lo; X.clip_hi[a] = hi;
+        }
+    }
+    int mode = R_EX;
+    if (accel) {
+        const cpm_volume_desc& vd = vol->desc;
+        CPM_REQUIRE(ctx, accel->have_range && accel->have_bits, "cpm_render_ex: the accel was never fully updated");
+        CPM_REQUIRE(ctx, accel->vol == vol && accel->tf == tf, "cpm_render_ex: the accel's last update saw another volume or TF");
+        CPM_REQUIRE(ctx, accel->dims[0] == vd.dims[0] && accel->dims[1] == vd.dims[1] && accel->dims[2] == vd.dims[2] && accel->dtype == vd.dtype,
+                    "cpm_render_ex: the accel was made for other dims or another voxel type");
+        CPM_REQUIRE(ctx, accel->tf_width == tf->width, "cpm_render_ex: the accel's last update saw another TF width");
+        mode |= R_SKIP;
+        X.bits = accel->bits;
+        X.lg = accel->lg;
+        X.nbx = accel->nb[0];
+        X.nbxy = accel->nb[0] * accel->nb[1];
+        X.last_bx = (float)((vd.dims[0] > 2 ? vd.dims[0] - 2 : 0) >> accel->lg);
+        X.last_by = (float)((vd.dims[1] > 2 ? vd.dims[1] - 2 : 0) >> accel->lg);
+        X.last_bz = (float)((vd.dims[2] > 2 ? vd.dims[2] - 2 : 0) >> accel->lg);
+        const size_t bits_bytes = (size_t)accel->n_words * sizeof(uint32_t);
+        if ((long long)bits_bytes <= (long long)ctx->dbg.render_bits_lds && lds + bits_bytes <= ctx->lds_per_block) {
+            X.bits_words = accel->n_words;
+            lds += bits_bytes;
+        }
+    }
+    if (stats) { mode |= R_STATS; X.stats = stats; }
+    hipStream_t s = (hipStream_t)stream;
+    rc = render_volume(ctx, vol, s, A);
+    if (rc) return rc;
+
+    const dim3 g(div_up(A.width, 16), div_up(A.height, 16)), b(256);
+#define CPM_RENDER_EX_LAUNCH_M(DT, CH)                                                                                    \
+    do {                                                                                                                  \
+        switch (mode) {                                                                                                   \
+            case R_EX: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX>), g, b, lds, s, A, X); break;                       \
+            case R_EX | R_SKIP: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX | R_SKIP>), g, b, lds, s, A, X); break;     \
+            case R_EX | R_STATS: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX | R_STATS>), g, b, lds, s, A, X); break;   \
+            default: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX | R_SKIP | R_STATS>), g, b, lds, s, A, X); break;      \
+        }                                                                                                                 \
+    } while (0)
+#define CPM_RENDER_EX_LAUNCH(DT)                                                                            \
+    do {                                                                                                    \
+        if (grid->channels == 1) CPM_RENDER_EX_LAUNCH_M(DT, 1);                                             \
+        else CPM_RENDER_EX_LAUNCH_M(DT, 4);                                                                 \
+    } while (0)
+    switch (vol->desc.dtype) {
+        case CPM_U8: CPM_RENDER_EX_LAUNCH(CPM_U8); break;
+        case CPM_U16: CPM_RENDER_EX_LAUNCH(CPM_U16); break;
+        case CPM_F16: CPM_RENDER_EX_LAUNCH(CPM_F16); break;
+        default: CPM_RENDER_EX_LAUNCH(CPM_F32); break;
+    }
+#undef CPM_RENDER_EX_LAUNCH
+#undef CPM_RENDER_EX_LAUNCH_M
+    CPM_LAUNCH_CHECK(ctx, "render_ex_kernel");
     return CPM_OK;
 }
 

@@ -164,6 +164,14 @@ int cpmh_render(cpmh_network* net, int width, int height, const float camera[11]
     std::memcpy(rgba_out, px.data(), px.size() * sizeof(float));
     return 0;
 }
+// cpmh_render with the raycaster's emptySpaceSkipping property set to skip_empty (0 / 1): with it on, the same bits through cpm_render_ex, camera
+// rays clipped to the tracer's clip box.
+int cpmh_render_ex(cpmh_network* net, int width, int height, const float camera[11], float sampling_rate, int skip_empty, float* rgba_out) {
+    if (!net) return -1;
+    net->raycaster.emptySpaceSkipping_.set(skip_empty != 0);
+    net->raycaster.setClipBox(net->tracer.clipBox());
+    return cpmh_render(net, width, height, camera, sampling_rate, rgba_out);
+}
 // the ndc -> texture matrix (column-major) of the last cpmh_render
 void cpmh_last_render_matrix(cpmh_network* net, float out[16]) { std::memcpy(out, net->raycaster.lastNdcToTexture().data(), 16 * sizeof(float)); }
 

@@ -1525,9 +1525,43 @@ LightingRaycasterHIP::LightingRaycasterHIP() {
     addProperty(lighting_);
     addProperty(channel_);
     addProperty(transferFunction_);
+    addProperty(emptySpaceSkipping_);
 }
 LightingRaycasterHIP::~LightingRaycasterHIP() {
+    if (accel_) cpm_render_accel_destroy(CpmRuntime::get().ctx(), accel_);
     if (tf_) cpm_tf_destroy(CpmRuntime::get().ctx(), tf_);
+}
+
+cpm_render_accel* LightingRaycasterHIP::freshAccel(cpm_volume* vol, bool tfChanged) {
+    auto& rt = CpmRuntime::get();
+    auto volume = volumePort_.getData();
+    const size3_t vd = volume->getDimensions();
+    const int32_t shape[4] = { (int32_t)vd.x, (int32_t)vd.y, (int32_t)vd.z, (int32_t)volume->dtype() };
+    if (accel_ && std::memcmp(shape, accelShape_, sizeof(shape)) != 0) {
+        cpm_render_accel_destroy(rt.ctx(), accel_);
+        accel_ = nullptr;
+    }
+    if (!accel_) {
+        cpm_volume_desc desc;
+        cpm_volume_desc_default(&desc, shape, shape[3]);
+        if (!rt.check(cpm_render_accel_create(rt.ctx(), &desc, 8, &accel_), "cpm_render_accel_create")) { accel_ = nullptr; return nullptr; }
+        std::memcpy(accelShape_, shape, sizeof(shape));
+        accelVol_ = nullptr;
+        accelHasTf_ = false;
+    }
+    // the volume inport: new data on the port, or another device representation behind the same data
+    const bool volChanged = volumePort_.changedSinceLastCheck() || vol != accelVol_;
+    tfChanged = tfChanged || !accelHasTf_;
+    if (volChanged || tfChanged) {
+        if (!rt.check(cpm_render_accel_update(rt.ctx(), accel_, volChanged ? vol : nullptr, tfChanged ? tf_ : nullptr, rt.stream()), "cpm_render_accel_update")) {
+            accelVol_ = nullptr;
+            accelHasTf_ = false;
+            return nullptr;
+        }
+        accelVol_ = vol;
+        accelHasTf_ = true;
+    }
+    return accel_;
 }
 
 void LightingRaycasterHIP::process() {
@@ -1539,7 +1573,10 @@ void LightingRaycasterHIP::process() {
     cpm_volume* vol = volume->getDeviceRepresentation();
     if (!vol) return;
     std::vector<float> lut = transferFunction_.get().lut(1024);
+    bool tfChanged = false;
     if (!tf_ || lut != tfLut_) {
+        tfChanged = true;
+        accelHasTf_ = false;
         if (!tf_) { if (!rt.check(cpm_tf_create(rt.ctx(), lut.data(), 1024, 0, rt.stream(), &tf_), "cpm_tf_create")) { tf_ = nullptr; return; } }
         else if (!rt.check(cpm_tf_update(rt.ctx(), tf_, lut.data(), 0, rt.stream()), "cpm_tf_update")) return;
         tfLut_ = std::move(lut);
@@ -1583,7 +1620,13 @@ void LightingRaycasterHIP::process() {
     d.sampling_rate = raycasting_.samplingRate;
     d.colored_light = lighting_.supportColoredLight ? 1 : 0;
     if (!image_ || image_->getDimensions().x != dims.x || image_->getDimensions().y != dims.y) image_ = std::make_shared<Image>(dims);
-    if (!rt.check(cpm_render(rt.ctx(), vol, tf_, light->data.device(), &g, &d, image_->color.device(), rt.stream()), "cpm_render")) return;
+    if (emptySpaceSkipping_.get()) {
+        cpm_render_options o{};
+        o.accel = freshAccel(vol, tfChanged);
+        if (!o.accel) return;
+        o.clip_aabb = clip_;
+        if (!rt.check(cpm_render_ex(rt.ctx(), vol, tf_, light->data.device(), &g, &d, &o, image_->color.device(), rt.stream()), "cpm_render_ex")) return;
+    } else if (!rt.check(cpm_render(rt.ctx(), vol, tf_, light->data.device(), &g, &d, image_->color.device(), rt.stream()), "cpm_render")) return;
     outport_.setData(image_);
 }
 

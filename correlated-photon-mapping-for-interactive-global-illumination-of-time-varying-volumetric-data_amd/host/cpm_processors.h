@@ -596,6 +596,9 @@ private:
     Buffer<int> nChanged_{ 1 };
     PhotonData::InvalidationReason invalidationFlag_ = PhotonData::InvalidationReason::All;
     float aabb_[8] = { 0, 0, 0, 1, 1, 1, 1, 1 };
+public:
+    const float* clipBox() const { return aabb_; }  // the clip ranges as the tracer's box (texture space)
+private:
     int remainingPhotonsOffset_ = 0, remainingPhotonsToUpdate_ = -1;
     bool remainingPending_ = false;  // the last evaluation was budgeted on the device: remainingPhotonsToUpdate_ comes with its count
     int hostWaits_ = 0;
@@ -698,6 +701,9 @@ private:
 // supported).  Rays come from the entry / exit points when both inports have data (EntryExitPoints images: RGBA32F texture
 // coordinates, alpha 0 = no hit), else from the camera (world space; textureToWorld = the volume's world * model matrix).
 // Not run by anything else in this library: a frame (cpmh_evaluate and the timing entry points) never renders.
+// emptySpaceSkipping (off by default: the images and timings of cpm_render stay): the same bits through cpm_render_ex with a
+// cpm_render_accel this processor owns -- its range grid follows the volume inport, its bits the TF property -- and camera rays clipped to
+// the volume's clip box (setClipBox: texture space, the tracer's aabb; Inviwo's raycaster gets the same from the clipped proxy geometry).
 class LightingRaycasterHIP : public Processor {
 public:
     LightingRaycasterHIP();
@@ -706,6 +712,8 @@ public:
     void process() override;
     // the ImageOutport's size (Inviwo takes it from the canvas the outport feeds)
     void setOutputDimensions(uvec2 d) { outDims_ = d; }
+    // the volume's clip box (min.xyz, 1, max.xyz, 1), used when emptySpaceSkipping is on
+    void setClipBox(const float aabb[8]) { for (int i = 0; i < 8; ++i) clip_[i] = aabb[i]; }
     // ndc -> texture matrix of the last camera-mode render (column-major)
     const std::array<float, 16>& lastNdcToTexture() const { return lastNdcToTexture_; }
     DataInport<Volume> volumePort_{ "volume" };
@@ -736,7 +744,15 @@ public:
     } lighting_;
     IntProperty channel_{ "channel", "Render channel", 0 };  // 0 only (the volumes of this path have one channel)
     TransferFunctionProperty transferFunction_{ "transferFunction", "Transfer function", TransferFunction() };
+    BoolProperty emptySpaceSkipping_{ "emptySpaceSkipping", "Empty-space skipping", false };
 private:
+    // the accel for `vol`, brought up to date with the volume inport and the TF; nullptr (error logged) on failure
+    cpm_render_accel* freshAccel(cpm_volume* vol, bool tfChanged);
+    float clip_[8] = { 0, 0, 0, 1, 1, 1, 1, 1 };
+    cpm_render_accel* accel_ = nullptr;
+    cpm_volume* accelVol_ = nullptr;      // what the accel's range grid was built from ...
+    int32_t accelShape_[4] = { 0, 0, 0, -1 };  // ... and the dims and voxel type it was created for
+    bool accelHasTf_ = false;
     uvec2 outDims_{ 256, 256 };
     std::shared_ptr<Image> image_;
     cpm_tf* tf_ = nullptr;

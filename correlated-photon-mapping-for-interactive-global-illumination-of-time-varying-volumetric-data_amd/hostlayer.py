@@ -49,6 +49,7 @@ def load():
         "cpmh_sequence_step": (i32, [vp, vp, C.c_float, vp]),
         "cpmh_sequence_step_total": (i32, [vp, vp, C.c_float, vp]),
         "cpmh_render": (i32, [vp, i32, i32, C.POINTER(C.c_float * 11), C.c_float, vp]),
+        "cpmh_render_ex": (i32, [vp, i32, i32, C.POINTER(C.c_float * 11), C.c_float, i32, vp]),
         "cpmh_last_render_matrix": (None, [vp, vp]),
     }
     for name, (res, args) in sigs.items():
@@ -169,12 +170,18 @@ class HostNetwork:
         text = self.lib.cpmh_profile_full_frames(self.h, reps).decode()
         return {k: float(v) for k, v in (item.split("=") for item in text.split(";") if item)}
 
-    def render(self, width, height, look_from, look_to, look_up=(0.0, 1.0, 0.0), fov_deg=38.0, aspect=None, sampling_rate=2.0):
+    def render(self, width, height, look_from, look_to, look_up=(0.0, 1.0, 0.0), fov_deg=38.0, aspect=None, sampling_rate=2.0, skip_empty=None):
         """LightingRaycasterHIP over the network's volume, TF and light volume as the last evaluate() left them:
-        (height, width, 4) float32 RGBA, row 0 = the bottom row (near / far: the processor's 0.1 / 100)."""
+        (height, width, 4) float32 RGBA, row 0 = the bottom row (near / far: the processor's 0.1 / 100).
+        skip_empty: True / False sets the processor's emptySpaceSkipping property first (cpmh_render_ex; with it on the rays are clipped to
+        the tracer's clip box); None leaves it as it is."""
         cam = (C.c_float * 11)(*look_from, *look_to, *look_up, fov_deg, width / height if aspect is None else aspect)
         out = np.empty((height, width, 4), np.float32)
-        if self.lib.cpmh_render(self.h, width, height, C.byref(cam), sampling_rate, out.ctypes.data) != 0:
+        if skip_empty is None:
+            rc = self.lib.cpmh_render(self.h, width, height, C.byref(cam), sampling_rate, out.ctypes.data)
+        else:
+            rc = self.lib.cpmh_render_ex(self.h, width, height, C.byref(cam), sampling_rate, int(bool(skip_empty)), out.ctypes.data)
+        if rc != 0:
             raise RuntimeError("cpmh_render failed")
         return out
 

@@ -75,6 +75,16 @@ def heterogeneous_volume(dim=256, blob_center=(0.5, 0.5, 0.5)) -> np.ndarray:
     return out
 
 
+def blob_volume(dim=256, blob_center=(0.5, 0.5, 0.5)) -> np.ndarray:
+    """The blob of heterogeneous_volume alone, over a constant 0: v = 0.75 exp(-|p - c|^2 / 0.02) at voxel centres, quantised to u8 --
+    a volume that is mostly one value (what empty-space skipping is for).  dim as in heterogeneous_volume; the array is [z, y, x]."""
+    dx, dy, dz = (dim, dim, dim) if np.isscalar(dim) else (int(dim[0]), int(dim[1]), int(dim[2]))
+    cx, cy, cz = [(np.arange(d, dtype=np.float64) + 0.5) / d for d in (dx, dy, dz)]
+    gx, gy, gz = (cx - blob_center[0]) ** 2, (cy - blob_center[1]) ** 2, (cz - blob_center[2]) ** 2
+    r2 = gz[:, None, None] + gy[None, :, None] + gx[None, None, :]
+    return np.rint(np.clip(0.75 * np.exp(-r2 / 0.02), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
 def sequence_blob_center(step: int, n_steps: int = 32):
     """Config 5: blob centre c_t = (0.3 + 0.4 t / (n - 1), 0.5, 0.5)."""
     return (0.3 + 0.4 * step / (n_steps - 1), 0.5, 0.5)

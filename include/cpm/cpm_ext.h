@@ -711,7 +711,7 @@ void cpm_gl_unregister(cpm_ctx* ctx, cpm_gl_resource* resource);
  *       early ray termination: the ray stops after the first sample with res.a > 0.99.
  * Output: res, premultiplied RGBA over transparent black.  No atomics: the same inputs give the same bits.
  * Not supported: gradient (Phong) shading (the light volume carries the illumination), the isosurface and MIP compositing modes,
- * depth output, channel != 0, empty-space skipping, handing the image to GL.
+ * depth output, channel != 0, handing the image to GL.  Empty-space skipping and a clip box: cpm_render_ex below.
  * Refused with CPM_ERR_INVALID_ARGUMENT, nothing written: a null volume, TF, light volume, grid, desc or output; grid channels not
  * 1 or 4; width or height <= 0 or width * height >= 2^31; a sampling rate <= 0 or not finite; a TF narrower than 2 texels; only one
  * of entry / exit; rgba_out (and a 4-channel light volume, entry, exit) not 16-byte aligned.  CPM_ERR_UNSUPPORTED: a TF whose
@@ -728,6 +728,45 @@ typedef struct cpm_render_desc {
 /* light_volume: cells * channels floats as cpm_gather writes it (channels fastest), described by grid (dims, channels). */
 int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
                const cpm_render_desc* desc, float* rgba_out, cpm_stream stream);
+
+/* ---- raycaster: empty-space skipping, clip box, sample counts (opt-in; cpm_render above is unchanged) ------------------------------
+ * cpm_render_accel: the skip structure of one volume shape (dims, voxel type) and brick size (4, 8 or 16 voxels; <= 0: 8).  Two parts:
+ *   - the range grid: per brick the min and max of the normalised voxel value (as the sampler sees it: norm, format offset and scaling
+ *     applied) over the brick's voxels plus the one-voxel apron at +x, +y, +z, clamped at the volume's edge -- every voxel a trilinear
+ *     footprint based in the brick reads.  A brick that holds a NaN or an infinity is never empty.  Rebuilt when the voxels change; it
+ *     reads the volume's linear block, so a footprint copy left stale by cpm_volume_mix stays stale.
+ *   - the empty bits: a brick is empty iff every TF texel i0(min) - 1 .. i0(max) + 2 (i0 = the sampler's texel floor; clamped to the TF)
+ *     has alpha exactly 0: the texels a value in the range can touch, widened by one texel on each side because an interpolated value
+ *     may leave the range of its eight voxels by a few ulps.  Rebuilt when the TF or the range grid changes.
+ * cpm_render_accel_update(vol, tf): a non-NULL volume rebuilds the range grid, a non-NULL TF its prefix count of non-zero alpha texels,
+ * either rebuilds the bits; NULL means "unchanged".  The first update needs both.  The accel remembers WHICH cpm_volume and cpm_tf
+ * objects (and which TF width) it saw.  Whether their CONTENTS are still what it saw is the caller's duty: after cpm_volume_update,
+ * cpm_volume_mix, a stream slot's reuse or cpm_tf_update of the same objects, call cpm_render_accel_update before the next render.
+ *
+ * cpm_render_ex = cpm_render with options (NULL, or all members NULL: the bits of cpm_render):
+ *   accel      the image has the bits of cpm_render; samples based in empty bricks are not evaluated.  A sample's brick is its footprint's
+ *              base voxel (the sampler's own floors) >> log2(brick).
+ *   clip_aabb  host, 8 floats (min.xyz, 1, max.xyz, 1) in texture space, the tracer's aabb: camera mode clips the segment to this box
+ *              instead of [0,1]^3 (the unit box gives the bits of no box).  Ignored with entry / exit buffers.
+ *   stats      device, 2 x uint32, ADDED to (the caller zeroes them): [0] samples evaluated (a volume fetch happened), [1] samples
+ *              skipped (always 0 without an accel).  The image is the same bits with and without.
+ * Refused with CPM_ERR_INVALID_ARGUMENT, nothing written: whatever cpm_render refuses; an accel that was never fully updated; an accel
+ * whose last update saw another cpm_volume or cpm_tf object, other dims or voxel type, or another TF width; a clip box that is not finite
+ * or has min >= max on an axis. */
+typedef struct cpm_render_accel cpm_render_accel;
+typedef struct cpm_render_options {
+    const cpm_render_accel* accel;   /* nullable */
+    const float* clip_aabb;          /* nullable: host, (min.xyz, 1, max.xyz, 1) */
+    uint32_t* stats;                 /* nullable: device, 2 words */
+} cpm_render_options;
+
+int cpm_render_accel_create(cpm_ctx* ctx, const cpm_volume_desc* desc, int brick, cpm_render_accel** out);
+void cpm_render_accel_destroy(cpm_ctx* ctx, cpm_render_accel* accel);
+int cpm_render_accel_update(cpm_ctx* ctx, cpm_render_accel* accel, const cpm_volume* vol, const cpm_tf* tf, cpm_stream stream);
+/* bricks (nullable): bricks along x, y, z; n_empty (nullable): the number of empty bricks (copies the bits back: synchronises). */
+int cpm_render_accel_info(cpm_ctx* ctx, const cpm_render_accel* accel, int32_t bricks[3], uint32_t* n_empty, cpm_stream stream);
+int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+                  const cpm_render_desc* desc, const cpm_render_options* options, float* rgba_out, cpm_stream stream);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,9 @@ void cpm_debug_set_sort_mode(cpm_ctx* ctx, int mode);
 void cpm_debug_set_sort_items(cpm_ctx* ctx, int items);
 /* streaming kernels (temporal mix): workgroups per CU; 0 = one vector per lane, -1 = by size (default) */
 void cpm_debug_set_stream_wg_per_cu(cpm_ctx* ctx, int n);
+/* cpm_render_ex with an accel: empty bits of up to max_bytes are staged into LDS behind the TF column, larger sets are read through L2
+ * (default 4096; 0 = never stage) */
+void cpm_debug_set_render_bits_lds(cpm_ctx* ctx, int max_bytes);
 /* test hook: the next cpm_photon_importance_select / _equal_select / _retrace call fails AFTER it has appended its tiles (what a
  * refused launch or a failed allocation does): the selection must then publish a count of 0 */
 void cpm_debug_fail_next_select(cpm_ctx* ctx, int on);
