@@ -9,6 +9,7 @@ fallback: when the shared library is missing the import fails loudly, and
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 from pathlib import Path
 
@@ -56,7 +57,7 @@ EXT_SYMBOLS = [
     "cpm_bricklist_reduce_exchange", "cpm_gather_fast_segment", "cpm_bricklist_segment_to_grid", "cpm_comm_send", "cpm_comm_recv",
     "cpm_light_volume_texels", "cpm_gl_available", "cpm_gl_register_buffer", "cpm_gl_acquire", "cpm_gl_release", "cpm_gl_buffer_pointer",
     "cpm_gl_copy_to_buffer", "cpm_gl_unregister", "cpm_render", "cpm_render_accel_create", "cpm_render_accel_destroy",
-    "cpm_render_accel_update", "cpm_render_accel_info", "cpm_render_ex"
+    "cpm_render_accel_update", "cpm_render_accel_info", "cpm_render_ex", "cpm_render_shaded"
 ]
 ABI_SYMBOLS = CORE_SYMBOLS + EXT_SYMBOLS
 CPM_GL_TEXEL_F32, CPM_GL_TEXEL_F16 = 0, 1
@@ -143,6 +144,61 @@ class RenderDesc(C.Structure):
 class RenderOptions(C.Structure):
     """cpm_render_options (include/cpm/cpm_ext.h): nullable accel, host clip box (8 floats), device stats (2 x uint32)."""
     _fields_ = [("accel", C.c_void_p), ("clip_aabb", C.POINTER(C.c_float)), ("stats", C.c_void_p)]
+
+
+class RenderShading(C.Structure):
+    """cpm_render_shading (include/cpm/cpm_ext.h): mode, texture -> world matrix (column-major, affine), world-space light position,
+    ambient / diffuse / specular colours, shininess."""
+    _fields_ = [("mode", C.c_int32), ("texture_to_world", C.c_float * 16), ("light_position", C.c_float * 3), ("ambient", C.c_float * 3),
+                ("diffuse", C.c_float * 3), ("specular", C.c_float * 3), ("shininess", C.c_float)]
+
+
+#: cpm_shade_mode
+SHADE_NONE, SHADE_AMBIENT, SHADE_DIFFUSE, SHADE_SPECULAR, SHADE_BLINN_PHONG, SHADE_PHONG = range(6)
+SHADE_MODES = {"none": SHADE_NONE, "ambient": SHADE_AMBIENT, "diffuse": SHADE_DIFFUSE, "specular": SHADE_SPECULAR,
+               "blinn_phong": SHADE_BLINN_PHONG, "phong": SHADE_PHONG}
+
+
+@dataclasses.dataclass
+class Shading:
+    """Gradient shading of a render (Context.render(shading=...), cpm_render_shaded): a mode (a name of SHADE_MODES or a cpm_shade_mode
+    number), the light's world-space position, the ambient / diffuse / specular colours (a number stands for a grey), the shininess and
+    the volume's texture -> world matrix as 16 floats, column-major (texture_to_world(); None: the identity).  The defaults are Inviwo's
+    SimpleLightingProperty's, except that nothing is shaded until a mode is chosen."""
+    mode: object = "none"
+    light_position: tuple = (0.0, 5.0, 5.0)
+    ambient: object = 0.15
+    diffuse: object = 0.6
+    specular: object = 0.4
+    shininess: float = 60.0
+    texture_to_world: object = None
+
+    def struct(self) -> RenderShading:
+        import numpy as np
+        h = RenderShading()
+        mode = self.mode
+        if isinstance(mode, str):
+            if mode.lower() not in SHADE_MODES:
+                raise ValueError(f"unknown shading mode {mode!r}: one of {sorted(SHADE_MODES)}")
+            mode = SHADE_MODES[mode.lower()]
+        h.mode = int(mode)
+        m = np.eye(4, dtype=np.float32).reshape(16) if self.texture_to_world is None else np.asarray(self.texture_to_world, np.float32).reshape(16)
+        h.texture_to_world[:] = m.tolist()
+        for name in ("light_position", "ambient", "diffuse", "specular"):
+            getattr(h, name)[:] = np.broadcast_to(np.asarray(getattr(self, name), np.float32), (3,)).tolist()
+        h.shininess = float(self.shininess)
+        return h
+
+
+def texture_to_world(model=None, world=None):
+    """The volume's texture -> world matrix, world * model, as 16 float32 column-major: what Shading.texture_to_world and
+    cpm_render_shading take.  model / world: the volume's 4x4 model and world matrices in numpy convention (row-major, M @ p; e.g. a
+    .u3d header's, transposed from its column-major storage); None: the identity.  The same product is camera_ndc_to_texture's
+    texture_to_world (there in numpy convention)."""
+    import numpy as np
+    m = np.eye(4) if model is None else np.asarray(model, np.float64).reshape(4, 4)
+    w = np.eye(4) if world is None else np.asarray(world, np.float64).reshape(4, 4)
+    return (w @ m).T.reshape(16).astype(np.float32)
 
 
 def camera_ndc_to_texture(look_from, look_to, look_up, fov_deg, aspect, near, far, texture_to_world=None):
@@ -412,6 +468,7 @@ def load_library() -> C.CDLL:
         "cpm_render_accel_update": (i32, [vp, vp, vp, vp, vp]),
         "cpm_render_accel_info": (i32, [vp, vp, P(C.c_int32 * 3), P(u32), vp]),
         "cpm_render_ex": (i32, [vp, vp, vp, vp, P(GridDesc), P(RenderDesc), P(RenderOptions), vp, vp]),
+        "cpm_render_shaded": (i32, [vp, vp, vp, vp, P(GridDesc), P(RenderDesc), P(RenderOptions), P(RenderShading), vp, vp]),
         "cpm_debug_set_render_bits_lds": (None, [vp, i32]),
         "cpm_volume_device_data": (vp, [vp, P(sz)]),
         "cpm_volume_download": (i32, [vp, vp, vp, vp]),
@@ -859,7 +916,7 @@ class Context:
         return RenderAccel(self, h, int(brick))
 
     def render(self, vol, tf, light_volume, grid: GridDesc, width, height, *, ndc_to_texture=None, entry=None, exit=None,
-               sampling_rate=1.0, colored_light=True, out=None, accel=None, clip=None, stats=None):
+               sampling_rate=1.0, colored_light=True, out=None, accel=None, clip=None, stats=None, shading=None):
         """cpm_render: the volume classified by `tf` and lit by `light_volume` (a float32 device tensor of cells * grid.channels,
         as the gather writes it) -> (height, width, 4) float32 premultiplied RGBA, row 0 = the bottom row.  Rays from the camera
         (ndc_to_texture: 16 floats, column-major, e.g. camera_ndc_to_texture) or from entry / exit device tensors of
@@ -867,7 +924,10 @@ class Context:
 
         accel (a RenderAccel, updated for this vol and tf), clip (8 floats: min.xyz, 1, max.xyz, 1 in texture space, the tracer's aabb)
         or stats (a device tensor of 2 x int32 / uint32 words the launch ADDS its evaluated / skipped sample counts to) route the call
-        to cpm_render_ex; with none of them it is cpm_render."""
+        to cpm_render_ex; with none of them it is cpm_render.
+
+        shading (a Shading, or a dict of its fields; default None: today's bits): gradient shading of the classified colour before the light
+        volume multiplies it -- cpm_render_shaded with the same options.  Mode "none" gives the bits of cpm_render_ex."""
         import numpy as np
         if (entry is None) != (exit is None):
             raise ValueError("entry and exit are given together")
@@ -890,7 +950,7 @@ class Context:
         d.exit = None if exit is None else self._ptr(exit, f32).value
         if out is None:
             out = self.torch.empty((max(int(height), 0), max(int(width), 0), 4), dtype=f32, device=self.device)
-        if accel is None and clip is None and stats is None:
+        if accel is None and clip is None and stats is None and shading is None:
             self._check(self.lib.cpm_render(self.h, vol.h, tf.h, self._ptr(light_volume, f32), C.byref(grid), C.byref(d), self._ptr(out, f32),
                                             self._stream()))
             return out
@@ -907,6 +967,11 @@ class Context:
             if stats.numel() != 2 or stats.element_size() != 4:
                 raise ValueError("stats must hold 2 x 32-bit words")
             o.stats = self._ptr(stats).value
+        if shading is not None:
+            sh = (Shading(**shading) if isinstance(shading, dict) else shading).struct()
+            self._check(self.lib.cpm_render_shaded(self.h, vol.h, tf.h, self._ptr(light_volume, f32), C.byref(grid), C.byref(d), C.byref(o),
+                                                   C.byref(sh), self._ptr(out, f32), self._stream()))
+            return out
         self._check(self.lib.cpm_render_ex(self.h, vol.h, tf.h, self._ptr(light_volume, f32), C.byref(grid), C.byref(d), C.byref(o),
                                            self._ptr(out, f32), self._stream()))   # (the call has consumed the clip box on return)
         return out

@@ -26,6 +26,15 @@
 //     L2; one word per sample.
 //   * R_STATS: samples evaluated / skipped, summed over the wave and added with one atomic per counter and wave.
 //   * the clip box: the slab test against (lo, hi) from the arguments instead of (0, 1).
+//
+// cpm_render_shaded adds R_SHADE (render_shaded_kernel: the same render_ex_body, one more argument block): gradient shading of the TF
+// colour behind c.a > 0, before the multiplication by the light volume.
+//   * the gradient is six more calls of the same sample_volume<DT> at p +- (1 / dim) e_a -- the contract is their bits, so nothing is
+//     shared between them.  They are independent of each other and of the light volume's eight loads, and all fourteen fetches are in
+//     flight together before the first is consumed (one lane has no other work to hide them behind: DESIGN.md).  CPM_SHADE_AMBIENT needs
+//     no gradient and fetches none.
+//   * the matrices, the light and the material ride in the kernel arguments: SGPRs, no loads in the loop.
+//   * the view vector is the ray's, so it is computed once per pixel; N, L, H, R once per shaded sample in float32 (v_rsq_f32, powf).
 #include "cpm_render_accel.h"
 #include "cpm_trace_body.hip.h"
 
@@ -115,7 +124,7 @@ CPM_DEV void slab(float o, float d, float lo, float hi, float& s0, float& s1) {
     s1 = min_(s1, max_(ta, tb));
 }
 
-enum { R_SKIP = 1, R_STATS = 2, R_EX = 4 };
+enum { R_SKIP = 1, R_STATS = 2, R_EX = 4, R_SHADE = 8 };
 
 // what cpm_render_ex adds to a launch
 struct RenderExArgs {
@@ -154,8 +163,79 @@ CPM_DEV float brick_exit(float e, float step, float dimf, int i, int lg, float l
     return su == 0.0f ? inf : (bound - u0) * __builtin_amdgcn_rcpf(su);
 }
 
+// what cpm_render_shaded adds to a launch (R_SHADE only)
+struct RenderShadeArgs {
+    int mode;                         // CPM_SHADE_AMBIENT .. CPM_SHADE_PHONG
+    float h[3];                       // 1 / dim: the central difference's offset along each axis
+    float s[3];                       // dim / 2: what the difference is multiplied by
+    float a[9];                       // texture -> world, linear part A, column-major (a[3 c + r])
+    float t[3];                       // ... and translation
+    float nit[9];                     // inverse transpose of A, column-major: normals
+    float light[3];                   // world space
+    float ka[3], kd[3], ks[3];
+    float shininess;
+};
+
+// m v, m column-major 3 x 3; sums in column order
+CPM_DEV void mul3(const float* m, float x, float y, float z, float& ox, float& oy, float& oz) {
+    ox = m[0] * x + m[3] * y + m[6] * z;
+    oy = m[1] * x + m[4] * y + m[7] * z;
+    oz = m[2] * x + m[5] * y + m[8] * z;
+}
+
+// v / |v|; the zero vector stays zero (a light at the sample's own position, L = -V)
+CPM_DEV void normalize0(float& x, float& y, float& z) {
+    const float l2 = x * x + y * y + z * z;
+    const float inv = l2 > 0.0f ? __builtin_amdgcn_rsqf(l2) : 0.0f;
+    x *= inv; y *= inv; z *= inv;
+}
+
+// central differences of the sampler itself: g_a = (S(p + h_a e_a) - S(p - h_a e_a)) * (dim_a / 2), six sample_volume values bit for bit.
+// One-sided at half magnitude where the sampler clamps (the volume's edge).
+template <int DT>
+CPM_DEV void sample_gradient(const VolDev& V, const RenderShadeArgs& S, float px, float py, float pz, float& gx, float& gy, float& gz) {
+    const float xp = sample_volume<DT>(V, px + S.h[0], py, pz), xm = sample_volume<DT>(V, px - S.h[0], py, pz);
+    const float yp = sample_volume<DT>(V, px, py + S.h[1], pz), ym = sample_volume<DT>(V, px, py - S.h[1], pz);
+    const float zp = sample_volume<DT>(V, px, py, pz + S.h[2]), zm = sample_volume<DT>(V, px, py, pz - S.h[2]);
+    gx = (xp - xm) * S.s[0];
+    gy = (yp - ym) * S.s[1];
+    gz = (zp - zm) * S.s[2];
+}
+
+// c = ka c + kd c |N.L| + ks spec, spec = |N.H|^s (Blinn) or max(R.V, 0)^s (Phong); (vx, vy, vz) = V, unit, world space.
+// A gradient of exactly +-0 in all three components leaves the ambient term alone: decided on g, before any matrix.
+CPM_DEV void shade(const RenderShadeArgs& S, float gx, float gy, float gz, float px, float py, float pz, float vx, float vy, float vz,
+                   float& cr, float& cg, float& cb) {
+    float dif = 0.0f, spec = 0.0f;
+    if (S.mode != CPM_SHADE_AMBIENT && !(gx == 0.0f && gy == 0.0f && gz == 0.0f)) {
+        // the gradient's scale is the data's: bring its largest component to [1/2, 1) first, so that the squares neither underflow nor overflow
+        const int e = __builtin_amdgcn_frexp_expf(max_(max_(__builtin_fabsf(gx), __builtin_fabsf(gy)), __builtin_fabsf(gz)));
+        float nx, ny, nz;
+        mul3(S.nit, __builtin_ldexpf(gx, -e), __builtin_ldexpf(gy, -e), __builtin_ldexpf(gz, -e), nx, ny, nz);
+        normalize0(nx, ny, nz);
+        float wx, wy, wz;
+        mul3(S.a, px, py, pz, wx, wy, wz);
+        float lx = S.light[0] - (wx + S.t[0]), ly = S.light[1] - (wy + S.t[1]), lz = S.light[2] - (wz + S.t[2]);
+        normalize0(lx, ly, lz);
+        const float nl = nx * lx + ny * ly + nz * lz;
+        if (S.mode != CPM_SHADE_SPECULAR) dif = __builtin_fabsf(nl);
+        if (S.mode == CPM_SHADE_BLINN_PHONG) {
+            float hx = lx + vx, hy = ly + vy, hz = lz + vz;
+            normalize0(hx, hy, hz);
+            spec = powf(__builtin_fabsf(nx * hx + ny * hy + nz * hz), S.shininess);
+        } else if (S.mode == CPM_SHADE_SPECULAR || S.mode == CPM_SHADE_PHONG) {
+            const float k = 2.0f * nl;
+            const float rv = (k * nx - lx) * vx + (k * ny - ly) * vy + (k * nz - lz) * vz;
+            spec = powf(max_(rv, 0.0f), S.shininess);
+        }
+    }
+    cr = S.ka[0] * cr + S.kd[0] * cr * dif + S.ks[0] * spec;
+    cg = S.ka[1] * cg + S.kd[1] * cg * dif + S.ks[1] * spec;
+    cb = S.ka[2] * cb + S.kd[2] * cb * dif + S.ks[2] * spec;
+}
+
 template <int DT, int CH, int MODE>
-CPM_DEV float4 render_pixel(const RenderArgs& A, const RenderExArgs& X, const float4* lut, const uint32_t* lbits, const int pi, const int pj,
+CPM_DEV float4 render_pixel(const RenderArgs& A, const RenderExArgs& X, const RenderShadeArgs& S, const float4* lut, const uint32_t* lbits, const int pi, const int pj,
                             const int pix, uint32_t& evaluated, uint32_t& skipped) {
     float ex, ey, ez, rx, ry, rz;
     bool hit;
@@ -194,6 +274,12 @@ CPM_DEV float4 render_pixel(const RenderArgs& A, const RenderExArgs& X, const fl
         const float tIncr = tEnd / nf;
         const float dirx = rx / tEnd, diry = ry / tEnd, dirz = rz / tEnd;
         const float expo = tIncr * kRefSamplingInterval;
+        float vx = 0.0f, vy = 0.0f, vz = 0.0f;  // V = -normalize(A dir): the ray's, in either ray mode
+        if (MODE & R_SHADE) {
+            mul3(S.a, dirx, diry, dirz, vx, vy, vz);
+            normalize0(vx, vy, vz);
+            vx = -vx; vy = -vy; vz = -vz;
+        }
         for (int k = 0; k < n; ++k) {
             float px, py, pz;
             sample_position(ex, ey, ez, dirx, diry, dirz, tIncr, k, px, py, pz);
@@ -229,7 +315,14 @@ CPM_DEV float4 render_pixel(const RenderArgs& A, const RenderExArgs& X, const fl
             if (ca > 0.0f) {
                 float lr, lg, lb;
                 sample_light<CH>(A, px, py, pz, lr, lg, lb);
-                const float cr = lerp_(lo.x, hi.x, a) * lr, cg = lerp_(lo.y, hi.y, a) * lg, cb = lerp_(lo.z, hi.z, a) * lb;
+                float cr = lerp_(lo.x, hi.x, a), cg = lerp_(lo.y, hi.y, a), cb = lerp_(lo.z, hi.z, a);
+                if (MODE & R_SHADE) {
+                    // the six fetches of the gradient and the light volume's eight above depend on p alone: all in flight together
+                    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+                    if (S.mode != CPM_SHADE_AMBIENT) sample_gradient<DT>(A.vol, S, px, py, pz, gx, gy, gz);
+                    shade(S, gx, gy, gz, px, py, pz, vx, vy, vz, cr, cg, cb);
+                }
+                cr = cr * lr; cg = cg * lg; cb = cb * lb;
                 // 1 - (1 - ca)^expo without the cancellation of 1 - pow(): the small opacities of fine sampling keep their digits
                 const float ap = -expm1f(expo * log1pf(-ca));
                 const float wgt = (1.0f - res.w) * ap;
@@ -257,11 +350,12 @@ __global__ __launch_bounds__(256) void render_kernel(const RenderArgs A) {
     const int pix = pj * A.width + pi;
     uint32_t evaluated = 0, skipped = 0;
     const RenderExArgs X{};
-    A.out[pix] = render_pixel<DT, CH, 0>(A, X, lut, nullptr, pi, pj, pix, evaluated, skipped);
+    const RenderShadeArgs S{};
+    A.out[pix] = render_pixel<DT, CH, 0>(A, X, S, lut, nullptr, pi, pj, pix, evaluated, skipped);
 }
 
 template <int DT, int CH, int MODE>
-__global__ __launch_bounds__(256) void render_ex_kernel(const RenderArgs A, const RenderExArgs X) {
+CPM_DEV void render_ex_body(const RenderArgs& A, const RenderExArgs& X, const RenderShadeArgs& S) {
     extern __shared__ float4 lut[];
     uint32_t* lbits = reinterpret_cast<uint32_t*>(lut + A.tf_width);
     for (int i = threadIdx.x; i < A.tf_width; i += 256) lut[i] = A.tf[i];
@@ -275,7 +369,7 @@ __global__ __launch_bounds__(256) void render_ex_kernel(const RenderArgs A, cons
     uint32_t evaluated = 0, skipped = 0;
     if (pi < A.width && pj < A.height) {
         const int pix = pj * A.width + pi;
-        A.out[pix] = render_pixel<DT, CH, MODE>(A, X, lut, lbits, pi, pj, pix, evaluated, skipped);
+        A.out[pix] = render_pixel<DT, CH, MODE>(A, X, S, lut, lbits, pi, pj, pix, evaluated, skipped);
     }
     if (MODE & R_STATS) {  // all 64 lanes are here again: the wave's sums, one atomic each
 #pragma unroll
@@ -288,6 +382,18 @@ __global__ __launch_bounds__(256) void render_ex_kernel(const RenderArgs A, cons
             if (MODE & R_SKIP) atomicAdd(&X.stats[1], skipped);
         }
     }
+}
+
+template <int DT, int CH, int MODE>
+__global__ __launch_bounds__(256) void render_ex_kernel(const RenderArgs A, const RenderExArgs X) {
+    const RenderShadeArgs S{};
+    render_ex_body<DT, CH, MODE>(A, X, S);
+}
+
+// MODE includes R_SHADE
+template <int DT, int CH, int MODE>
+__global__ __launch_bounds__(256) void render_shaded_kernel(const RenderArgs A, const RenderExArgs X, const RenderShadeArgs S) {
+    render_ex_body<DT, CH, MODE>(A, X, S);
 }
 
 }  // namespace
@@ -377,13 +483,65 @@ int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const floa
 
 void cpm_debug_set_render_bits_lds(cpm_ctx* ctx, int max_bytes) { if (ctx) ctx->dbg.render_bits_lds = max_bytes; }
 
-int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
-                  const cpm_render_desc* desc, const cpm_render_options* options, float* rgba_out, cpm_stream stream) {
-    CPM_ENTER(ctx);
+}  // extern "C"
+
+// texture_to_world (column-major, affine) -> the kernel's A, t and inverse transpose of A (in double, rounded once); false: not finite, a
+// last row other than (0, 0, 0, 1), or a singular A
+static bool shade_matrices(const float* m, RenderShadeArgs& S) {
+    for (int i = 0; i < 16; ++i) if (!(m[i] - m[i] == 0.0f)) return false;
+    if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f) return false;
+    double a[3][3];  // [row][col]
+    for (int c = 0; c < 3; ++c)
+        for (int r = 0; r < 3; ++r) { a[r][c] = m[4 * c + r]; S.a[3 * c + r] = m[4 * c + r]; }
+    for (int r = 0; r < 3; ++r) S.t[r] = m[12 + r];
+    double cof[3][3];  // cofactors: inverse transpose = cof / det
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+            cof[r][c] = a[r1][c1] * a[r2][c2] - a[r1][c2] * a[r2][c1];
+        }
+    const double det = a[0][0] * cof[0][0] + a[0][1] * cof[0][1] + a[0][2] * cof[0][2];
+    if (det == 0.0 || !(det - det == 0.0)) return false;
+    for (int c = 0; c < 3; ++c)
+        for (int r = 0; r < 3; ++r) {
+            const float v = (float)(cof[r][c] / det);
+            if (!(v - v == 0.0f)) return false;
+            S.nit[3 * c + r] = v;
+        }
+    return true;
+}
+
+// cpm_render_ex and cpm_render_shaded: shading == NULL or CPM_SHADE_NONE launches render_ex_kernel
+static int render_ex_impl(cpm_ctx* ctx, const char* who, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+                          const cpm_render_desc* desc, const cpm_render_options* options, const cpm_render_shading* shading, float* rgba_out,
+                          cpm_stream stream) {
     RenderArgs A{};
     size_t lds = 0;
-    int rc = render_prepare(ctx, "cpm_render_ex", vol, tf, light_volume, grid, desc, rgba_out, A, lds);
+    int rc = render_prepare(ctx, who, vol, tf, light_volume, grid, desc, rgba_out, A, lds);
     if (rc) return rc;
+    // a refusal of this layer, under the name of the entry point that was called
+    auto refuse = [&](const char* why) { return set_error(ctx, CPM_ERR_INVALID_ARGUMENT, who, why); };
+    RenderShadeArgs S{};
+    if (shading) {
+        const cpm_render_shading& H = *shading;
+        CPM_REQUIRE(ctx, H.mode >= CPM_SHADE_NONE && H.mode <= CPM_SHADE_PHONG, "cpm_render_shaded: unknown shading mode");
+        if (H.mode != CPM_SHADE_NONE) {
+            for (int a = 0; a < 3; ++a) {
+                const float f[4] = { H.light_position[a], H.ambient[a], H.diffuse[a], H.specular[a] };
+                for (float v : f) CPM_REQUIRE(ctx, v - v == 0.0f, "cpm_render_shaded: the light position and the colours must be finite");
+                S.light[a] = f[0]; S.ka[a] = f[1]; S.kd[a] = f[2]; S.ks[a] = f[3];
+            }
+            CPM_REQUIRE(ctx, H.shininess > 0.0f && H.shininess <= 3.402823466e+38f, "cpm_render_shaded: shininess must be finite and > 0");
+            CPM_REQUIRE(ctx, shade_matrices(H.texture_to_world, S),
+                        "cpm_render_shaded: texture_to_world must be finite and affine (last row 0 0 0 1) with an invertible linear part");
+            S.mode = H.mode;
+            S.shininess = H.shininess;
+            for (int a = 0; a < 3; ++a) {
+                S.h[a] = 1.0f / (float)vol->desc.dims[a];
+                S.s[a] = 0.5f * (float)vol->desc.dims[a];
+            }
+        }
+    }
     const cpm_render_accel* accel = options ? options->accel : nullptr;
     const float* clip = options ? options->clip_aabb : nullptr;
     uint32_t* stats = options ? options->stats : nullptr;
@@ -392,18 +550,18 @@ int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const f
     if (clip) {
         for (int a = 0; a < 3; ++a) {
             const float lo = clip[a], hi = clip[4 + a];
-            CPM_REQUIRE(ctx, lo - lo == 0.0f && hi - hi == 0.0f && lo < hi, "cpm_render_ex: the clip box must be finite with min < max on every axis");
+            if (!(lo - lo == 0.0f && hi - hi == 0.0f && lo < hi)) return refuse("the clip box must be finite with min < max on every axis");
             X.clip_lo[a] = lo; X.clip_hi[a] = hi;
         }
     }
-    int mode = R_EX;
+    int mode = R_EX | (S.mode != CPM_SHADE_NONE ? R_SHADE : 0);
     if (accel) {
         const cpm_volume_desc& vd = vol->desc;
-        CPM_REQUIRE(ctx, accel->have_range && accel->have_bits, "cpm_render_ex: the accel was never fully updated");
-        CPM_REQUIRE(ctx, accel->vol == vol && accel->tf == tf, "cpm_render_ex: the accel's last update saw another volume or TF");
-        CPM_REQUIRE(ctx, accel->dims[0] == vd.dims[0] && accel->dims[1] == vd.dims[1] && accel->dims[2] == vd.dims[2] && accel->dtype == vd.dtype,
-                    "cpm_render_ex: the accel was made for other dims or another voxel type");
-        CPM_REQUIRE(ctx, accel->tf_width == tf->width, "cpm_render_ex: the accel's last update saw another TF width");
+        if (!(accel->have_range && accel->have_bits)) return refuse("the accel was never fully updated");
+        if (!(accel->vol == vol && accel->tf == tf)) return refuse("the accel's last update saw another volume or TF");
+        if (!(accel->dims[0] == vd.dims[0] && accel->dims[1] == vd.dims[1] && accel->dims[2] == vd.dims[2] && accel->dtype == vd.dtype))
+            return refuse("the accel was made for other dims or another voxel type");
+        if (!(accel->tf_width == tf->width)) return refuse("the accel's last update saw another TF width");
         mode |= R_SKIP;
         X.bits = accel->bits;
         X.lg = accel->lg;
@@ -430,7 +588,11 @@ int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const f
             case R_EX: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX>), g, b, lds, s, A, X); break;                       \
             case R_EX | R_SKIP: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX | R_SKIP>), g, b, lds, s, A, X); break;     \
             case R_EX | R_STATS: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX | R_STATS>), g, b, lds, s, A, X); break;   \
-            default: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX | R_SKIP | R_STATS>), g, b, lds, s, A, X); break;      \
+            case R_EX | R_SKIP | R_STATS: CPM_LAUNCH(ctx, (render_ex_kernel<DT, CH, R_EX | R_SKIP | R_STATS>), g, b, lds, s, A, X); break; \
+            case R_SHADE | R_EX: CPM_LAUNCH(ctx, (render_shaded_kernel<DT, CH, R_SHADE | R_EX>), g, b, lds, s, A, X, S); break; \
+            case R_SHADE | R_EX | R_SKIP: CPM_LAUNCH(ctx, (render_shaded_kernel<DT, CH, R_SHADE | R_EX | R_SKIP>), g, b, lds, s, A, X, S); break; \
+            case R_SHADE | R_EX | R_STATS: CPM_LAUNCH(ctx, (render_shaded_kernel<DT, CH, R_SHADE | R_EX | R_STATS>), g, b, lds, s, A, X, S); break; \
+            default: CPM_LAUNCH(ctx, (render_shaded_kernel<DT, CH, R_SHADE | R_EX | R_SKIP | R_STATS>), g, b, lds, s, A, X, S); break; \
         }                                                                                                                 \
     } while (0)
 #define CPM_RENDER_EX_LAUNCH(DT)                                                                            \
@@ -446,8 +608,23 @@ int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const f
     }
 #undef CPM_RENDER_EX_LAUNCH
 #undef CPM_RENDER_EX_LAUNCH_M
-    CPM_LAUNCH_CHECK(ctx, "render_ex_kernel");
+    CPM_LAUNCH_CHECK(ctx, mode & R_SHADE ? "render_shaded_kernel" : "render_ex_kernel");
     return CPM_OK;
+}
+
+extern "C" {
+
+int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+                  const cpm_render_desc* desc, const cpm_render_options* options, float* rgba_out, cpm_stream stream) {
+    CPM_ENTER(ctx);
+    return render_ex_impl(ctx, "cpm_render_ex", vol, tf, light_volume, grid, desc, options, nullptr, rgba_out, stream);
+}
+
+int cpm_render_shaded(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+                      const cpm_render_desc* desc, const cpm_render_options* options, const cpm_render_shading* shading, float* rgba_out,
+                      cpm_stream stream) {
+    CPM_ENTER(ctx);
+    return render_ex_impl(ctx, "cpm_render_shaded", vol, tf, light_volume, grid, desc, options, shading, rgba_out, stream);
 }
 
 }  // extern "C"

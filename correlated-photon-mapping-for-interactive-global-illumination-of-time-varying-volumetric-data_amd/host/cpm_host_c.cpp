@@ -175,16 +175,39 @@ int cpmh_render_ex(cpmh_network* net, int width, int height, const float camera[
 // the ndc -> texture matrix (column-major) of the last cpmh_render
 void cpmh_last_render_matrix(cpmh_network* net, float out[16]) { std::memcpy(out, net->raycaster.lastNdcToTexture().data(), 16 * sizeof(float)); }
 
+// the texture -> world matrix (column-major) the last cpmh_render had from its volume: what its shading was given
+void cpmh_last_render_texture_to_world(cpmh_network* net, float out[16]) { std::memcpy(out, net->raycaster.lastTextureToWorld().data(), 16 * sizeof(float)); }
+
+// The model and world matrices (column-major) of the network's volume: what the raycaster's camera and shading see as texture -> world
+// (world * model).  The photon path works in texture space; the light volume carries them along unread.
+void cpmh_set_volume_matrices(cpmh_network* net, const float model[16], const float world[16]) {
+    mat4 m, w;
+    for (int i = 0; i < 16; ++i) { m[i] = model[i]; w[i] = world[i]; }
+    net->volume->setModelMatrix(m);
+    net->volume->setWorldMatrix(w);
+}
+
+// "tracer", "lightvolume" or "raycaster" (members of a composite property by their own ids); -1: no such processor, -2: no such property
+static Processor* facade_processor(cpmh_network* net, const char* processor) {
+    return !strcmp(processor, "tracer") ? (Processor*)&net->tracer : !strcmp(processor, "lightvolume") ? (Processor*)&net->lightVolume
+         : !strcmp(processor, "raycaster") ? (Processor*)&net->raycaster : nullptr;
+}
 int cpmh_set_property_float(cpmh_network* net, const char* processor, const char* id, float value) {
-    Processor* p = !strcmp(processor, "tracer") ? (Processor*)&net->tracer : !strcmp(processor, "lightvolume") ? (Processor*)&net->lightVolume : nullptr;
+    Processor* p = facade_processor(net, processor);
     if (!p) return -1;
     if (auto* f = dynamic_cast<FloatProperty*>(p->getPropertyByIdentifier(id))) { f->set(value); return 0; }
     if (auto* i = dynamic_cast<IntProperty*>(p->getPropertyByIdentifier(id))) { i->set((int)value); return 0; }
     if (auto* b = dynamic_cast<BoolProperty*>(p->getPropertyByIdentifier(id))) { b->set(value != 0.f); return 0; }
     return -2;
 }
+int cpmh_set_property_vec3(cpmh_network* net, const char* processor, const char* id, const float value[3]) {
+    Processor* p = facade_processor(net, processor);
+    if (!p) return -1;
+    if (auto* v = dynamic_cast<FloatVec3Property*>(p->getPropertyByIdentifier(id))) { v->set(vec3(value[0], value[1], value[2])); return 0; }
+    return -2;
+}
 int cpmh_set_property_string(cpmh_network* net, const char* processor, const char* id, const char* value) {
-    Processor* p = !strcmp(processor, "lightvolume") ? (Processor*)&net->lightVolume : !strcmp(processor, "tracer") ? (Processor*)&net->tracer : nullptr;
+    Processor* p = facade_processor(net, processor);
     if (!p) return -1;
     if (auto* s = dynamic_cast<StringOptionProperty*>(p->getPropertyByIdentifier(id))) { s->set(value); return 0; }
     return -2;

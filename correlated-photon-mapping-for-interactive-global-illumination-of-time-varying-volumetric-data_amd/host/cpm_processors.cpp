@@ -1586,6 +1586,18 @@ void LightingRaycasterHIP::process() {
     const int32_t gd[3] = { (int32_t)ld.x, (int32_t)ld.y, (int32_t)ld.z };
     cpm_grid_desc_default(&g, gd, light->channels);
 
+    const mat4 t2w = [&] {
+        const mat4 &w = volume->getWorldMatrix(), &m = volume->getModelMatrix();
+        mat4 r{};
+        for (int c = 0; c < 4; ++c)
+            for (int row = 0; row < 4; ++row) {
+                float v = 0;
+                for (int k = 0; k < 4; ++k) v += w[4 * k + row] * m[4 * c + k];
+                r[4 * c + row] = v;
+            }
+        return r;
+    }();
+    for (int i = 0; i < 16; ++i) lastTextureToWorld_[i] = t2w[i];
     cpm_render_desc d{};
     const bool buffers = entryPort_.isReady() && exitPort_.isReady();
     uvec2 dims = outDims_;
@@ -1597,17 +1609,6 @@ void LightingRaycasterHIP::process() {
         d.entry = en->color.device();
         d.exit = ex->color.device();
     } else {
-        const mat4 t2w = [&] {
-            const mat4 &w = volume->getWorldMatrix(), &m = volume->getModelMatrix();
-            mat4 r{};
-            for (int c = 0; c < 4; ++c)
-                for (int row = 0; row < 4; ++row) {
-                    float v = 0;
-                    for (int k = 0; k < 4; ++k) v += w[4 * k + row] * m[4 * c + k];
-                    r[4 * c + row] = v;
-                }
-            return r;
-        }();
         if (!cameraNdcToTexture(camera_.lookFrom, camera_.lookTo, camera_.lookUp, camera_.fov, camera_.aspectRatio, camera_.nearPlane,
                                 camera_.farPlane, t2w, lastNdcToTexture_)) {
             LogError("LightingRaycasterHIP: the camera matrix is singular");
@@ -1620,7 +1621,26 @@ void LightingRaycasterHIP::process() {
     d.sampling_rate = raycasting_.samplingRate;
     d.colored_light = lighting_.supportColoredLight ? 1 : 0;
     if (!image_ || image_->getDimensions().x != dims.x || image_->getDimensions().y != dims.y) image_ = std::make_shared<Image>(dims);
-    if (emptySpaceSkipping_.get()) {
+    if (lighting_.shadingMode.get() != CPM_SHADE_NONE) {
+        cpm_render_options o{};
+        if (emptySpaceSkipping_.get()) {
+            o.accel = freshAccel(vol, tfChanged);
+            if (!o.accel) return;
+            o.clip_aabb = clip_;
+        }
+        cpm_render_shading sh{};
+        sh.mode = lighting_.shadingMode.get();
+        std::memcpy(sh.texture_to_world, lastTextureToWorld_.data(), sizeof(sh.texture_to_world));
+        const vec3 lp = lighting_.lightPosition.get(), ka = lighting_.lightColorAmbient.get(), kd = lighting_.lightColorDiffuse.get(),
+                   ks = lighting_.lightColorSpecular.get();
+        const float v[4][3] = { { lp.x, lp.y, lp.z }, { ka.x, ka.y, ka.z }, { kd.x, kd.y, kd.z }, { ks.x, ks.y, ks.z } };
+        std::memcpy(sh.light_position, v[0], sizeof(v[0]));
+        std::memcpy(sh.ambient, v[1], sizeof(v[1]));
+        std::memcpy(sh.diffuse, v[2], sizeof(v[2]));
+        std::memcpy(sh.specular, v[3], sizeof(v[3]));
+        sh.shininess = lighting_.materialShininess.get();
+        if (!rt.check(cpm_render_shaded(rt.ctx(), vol, tf_, light->data.device(), &g, &d, &o, &sh, image_->color.device(), rt.stream()), "cpm_render_shaded")) return;
+    } else if (emptySpaceSkipping_.get()) {
         cpm_render_options o{};
         o.accel = freshAccel(vol, tfChanged);
         if (!o.accel) return;

@@ -704,6 +704,7 @@ private:
 // emptySpaceSkipping (off by default: the images and timings of cpm_render stay): the same bits through cpm_render_ex with a
 // cpm_render_accel this processor owns -- its range grid follows the volume inport, its bits the TF property -- and camera rays clipped to
 // the volume's clip box (setClipBox: texture space, the tracer's aabb; Inviwo's raycaster gets the same from the clipped proxy geometry).
+// lighting.shadingMode other than none: gradient shading through cpm_render_shaded with the volume's texture -> world matrix.
 class LightingRaycasterHIP : public Processor {
 public:
     LightingRaycasterHIP();
@@ -716,6 +717,8 @@ public:
     void setClipBox(const float aabb[8]) { for (int i = 0; i < 8; ++i) clip_[i] = aabb[i]; }
     // ndc -> texture matrix of the last camera-mode render (column-major)
     const std::array<float, 16>& lastNdcToTexture() const { return lastNdcToTexture_; }
+    // texture -> world matrix (the volume's world * model, column-major) of the last render: what shading was given
+    const std::array<float, 16>& lastTextureToWorld() const { return lastTextureToWorld_; }
     DataInport<Volume> volumePort_{ "volume" };
     DataInport<Image> entryPort_{ "entry-points" };
     DataInport<Image> exitPort_{ "exit-points" };
@@ -738,9 +741,21 @@ public:
         FloatProperty nearPlane{ "near", "Near plane", 0.1f };
         FloatProperty farPlane{ "far", "Far plane", 100.0f };
     } camera_;
+    // Inviwo's SimpleLightingProperty ids and defaults, except shadingMode: none here (Inviwo: Phong), so that the processor's images and
+    // timings stay what cpm_render gives until shading is asked for.  shadingMode takes cpm_shade_mode's numbers (0 none, 1 ambient,
+    // 2 diffuse, 3 specular, 4 Blinn-Phong, 5 Phong: the order of Inviwo's ShadingMode); lightPosition is in world space.
     struct LightingProperty : CompositeProperty {
-        LightingProperty() : CompositeProperty("lighting", "Lighting") { addProperty(supportColoredLight); }
+        LightingProperty() : CompositeProperty("lighting", "Lighting") {
+            addProperty(supportColoredLight); addProperty(shadingMode); addProperty(lightPosition); addProperty(lightColorAmbient);
+            addProperty(lightColorDiffuse); addProperty(lightColorSpecular); addProperty(materialShininess);
+        }
         BoolProperty supportColoredLight{ "supportColoredLight", "Enable colored light", true };
+        IntProperty shadingMode{ "shadingMode", "Shading", 0 };
+        FloatVec3Property lightPosition{ "lightPosition", "Position", vec3(0.0f, 5.0f, 5.0f) };
+        FloatVec3Property lightColorAmbient{ "lightColorAmbient", "Ambient color", vec3(0.15f) };
+        FloatVec3Property lightColorDiffuse{ "lightColorDiffuse", "Diffuse color", vec3(0.6f) };
+        FloatVec3Property lightColorSpecular{ "lightColorSpecular", "Specular color", vec3(0.4f) };
+        FloatProperty materialShininess{ "materialShininess", "Shininess", 60.0f };
     } lighting_;
     IntProperty channel_{ "channel", "Render channel", 0 };  // 0 only (the volumes of this path have one channel)
     TransferFunctionProperty transferFunction_{ "transferFunction", "Transfer function", TransferFunction() };
@@ -758,6 +773,7 @@ private:
     cpm_tf* tf_ = nullptr;
     std::vector<float> tfLut_;
     std::array<float, 16> lastNdcToTexture_{};
+    std::array<float, 16> lastTextureToWorld_{};
 };
 
 }  // namespace inviwo

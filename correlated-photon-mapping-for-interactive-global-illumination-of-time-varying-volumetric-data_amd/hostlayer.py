@@ -22,6 +22,7 @@ def load():
         "cpmh_set_transfer_function": (None, [vp, vp, i32]),
         "cpmh_set_property_float": (i32, [vp, C.c_char_p, C.c_char_p, C.c_float]),
         "cpmh_set_property_string": (i32, [vp, C.c_char_p, C.c_char_p, C.c_char_p]),
+        "cpmh_set_property_vec3": (i32, [vp, C.c_char_p, C.c_char_p, C.POINTER(C.c_float * 3)]),
         "cpmh_n_photons": (i32, [vp]),
         "cpmh_n_recomputed": (i32, [vp]),
         "cpmh_remaining": (i32, [vp]),
@@ -51,6 +52,8 @@ def load():
         "cpmh_render": (i32, [vp, i32, i32, C.POINTER(C.c_float * 11), C.c_float, vp]),
         "cpmh_render_ex": (i32, [vp, i32, i32, C.POINTER(C.c_float * 11), C.c_float, i32, vp]),
         "cpmh_last_render_matrix": (None, [vp, vp]),
+        "cpmh_last_render_texture_to_world": (None, [vp, vp]),
+        "cpmh_set_volume_matrices": (None, [vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(lib, name)
@@ -85,6 +88,21 @@ class HostNetwork:
     def set_string(self, processor: str, prop: str, value: str):
         if self.lib.cpmh_set_property_string(self.h, processor.encode(), prop.encode(), value.encode()) != 0:
             raise KeyError(f"{processor}.{prop}")
+
+    def set_vec3(self, processor: str, prop: str, value):
+        if self.lib.cpmh_set_property_vec3(self.h, processor.encode(), prop.encode(), C.byref((C.c_float * 3)(*value))) != 0:
+            raise KeyError(f"{processor}.{prop}")
+
+    def set_shading(self, mode, light_position=None, ambient=None, diffuse=None, specular=None, shininess=None):
+        """The raycaster's `lighting` properties (Inviwo's SimpleLightingProperty ids): shadingMode (a name of binding.SHADE_MODES or its
+        number; "none", the default, keeps cpm_render's images), and whichever of the others are given."""
+        self.set_float("raycaster", "shadingMode", B.SHADE_MODES[mode.lower()] if isinstance(mode, str) else int(mode))
+        for prop, v in (("lightPosition", light_position), ("lightColorAmbient", ambient), ("lightColorDiffuse", diffuse),
+                        ("lightColorSpecular", specular)):
+            if v is not None:
+                self.set_vec3("raycaster", prop, np.broadcast_to(np.asarray(v, np.float32), (3,)).tolist())
+        if shininess is not None:
+            self.set_float("raycaster", "materialShininess", shininess)
 
     def set_transfer_function(self, tf_points):
         pts = np.ascontiguousarray(np.asarray(tf_points, np.float32))
@@ -189,6 +207,18 @@ class HostNetwork:
         """ndc -> texture matrix (16 float32, column-major) of the last render()."""
         m = np.empty(16, np.float32)
         self.lib.cpmh_last_render_matrix(self.h, m.ctypes.data)
+        return m
+
+    def set_volume_matrices(self, model=None, world=None):
+        """The volume's model and world matrices, 4x4 in numpy convention (M @ p; None: identity): the raycaster's texture -> world is
+        world @ model."""
+        m, w = (np.ascontiguousarray((np.eye(4) if x is None else np.asarray(x, np.float64).reshape(4, 4)).T, np.float32) for x in (model, world))
+        self.lib.cpmh_set_volume_matrices(self.h, m.ctypes.data, w.ctypes.data)
+
+    def last_render_texture_to_world(self):
+        """texture -> world matrix (16 float32, column-major) of the volume the last render() saw."""
+        m = np.empty(16, np.float32)
+        self.lib.cpmh_last_render_texture_to_world(self.h, m.ctypes.data)
         return m
 
     def add_light(self, light_position, light_direction):

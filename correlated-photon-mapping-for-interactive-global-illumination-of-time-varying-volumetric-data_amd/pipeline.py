@@ -342,14 +342,15 @@ class PhotonFrame:
         return self.light_volume
 
     def render(self, width, height, *, ndc_to_texture=None, entry=None, exit=None, sampling_rate=1.0, colored_light=True, out=None,
-               skip_empty=False, clip=None, stats=None):
+               skip_empty=False, clip=None, stats=None, shading=None):
         """This frame's volume, TF and light volume (as the last frame left it) raycast into a (height, width, 4) float32 image
         (binding.Context.render, cpm_render).  Not part of a frame: nothing here runs unless called.
 
         skip_empty=True: the same bits through cpm_render_ex with a skip structure this frame owns; whichever half of it the frame's
         own edits (a TF edit, a time step, a mix into the volume, a streamed acquire swapped in) have outdated is rebuilt first, and
         camera rays are clipped to the frame's aabb unless `clip` says otherwise.  clip: a box like the tracer's aabb (default: none,
-        the unit cube)."""
+        the unit cube).  shading: a binding.Shading (or a dict of its fields) -- gradient shading of the classified colour
+        (cpm_render_shaded); None, the default, keeps today's bits."""
         accel = None
         if skip_empty:
             accel = getattr(self, "_render_accel", None)
@@ -364,7 +365,7 @@ class PhotonFrame:
                 clip = self.aabb
         return self.ctx.render(self.vol, self.tf, self.light_volume, self.grid, width, height, ndc_to_texture=ndc_to_texture,
                                entry=entry, exit=exit, sampling_rate=sampling_rate, colored_light=colored_light, out=out,
-                               accel=accel, clip=clip, stats=stats)
+                               accel=accel, clip=clip, stats=stats, shading=shading)
 
     def splat(self, out=None, all_interactions=False):
         """Reference formulation (atomic splat), for comparison: clear + splat.

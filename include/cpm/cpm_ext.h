@@ -710,8 +710,8 @@ void cpm_gl_unregister(cpm_ctx* ctx, cpm_gl_resource* resource);
  *       res.rgb += (1 - res.a) a' c.rgb, res.a += (1 - res.a) a';
  *       early ray termination: the ray stops after the first sample with res.a > 0.99.
  * Output: res, premultiplied RGBA over transparent black.  No atomics: the same inputs give the same bits.
- * Not supported: gradient (Phong) shading (the light volume carries the illumination), the isosurface and MIP compositing modes,
- * depth output, channel != 0, handing the image to GL.  Empty-space skipping and a clip box: cpm_render_ex below.
+ * Not supported: the isosurface and MIP compositing modes, depth output, channel != 0, handing the image to GL.  Empty-space skipping
+ * and a clip box: cpm_render_ex below; gradient (Phong) shading: cpm_render_shaded below (cpm_render itself does not shade).
  * Refused with CPM_ERR_INVALID_ARGUMENT, nothing written: a null volume, TF, light volume, grid, desc or output; grid channels not
  * 1 or 4; width or height <= 0 or width * height >= 2^31; a sampling rate <= 0 or not finite; a TF narrower than 2 texels; only one
  * of entry / exit; rgba_out (and a 4-channel light volume, entry, exit) not 16-byte aligned.  CPM_ERR_UNSUPPORTED: a TF whose
@@ -767,6 +767,50 @@ int cpm_render_accel_update(cpm_ctx* ctx, cpm_render_accel* accel, const cpm_vol
 int cpm_render_accel_info(cpm_ctx* ctx, const cpm_render_accel* accel, int32_t bricks[3], uint32_t* n_empty, cpm_stream stream);
 int cpm_render_ex(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
                   const cpm_render_desc* desc, const cpm_render_options* options, float* rgba_out, cpm_stream stream);
+
+/* ---- raycaster: gradient shading, the Phong family (opt-in; cpm_render and cpm_render_ex above are unchanged) -----------------------
+ * cpm_render_shaded = cpm_render_ex plus local shading of the classified colour: behind c.a > 0, between the TF lookup and the
+ * multiplication by the light volume, c.rgb = shade(c.rgb), then c.rgb *= L as before.  Rays, sample positions, the sampler, the TF
+ * lookup, opacity correction, compositing and early termination are cpm_render's.  The rules are this build's own, assumed from
+ * Inviwo's LightingRaycaster defaults and not checked against an Inviwo.  All arithmetic is float32.
+ *   gradient   g_a = (S(p + h_a e_a) - S(p - h_a e_a)) * (dim_a / 2), h_a = 1 / dim_a, in texture space; S is the sampler of cpm_render
+ *              at the float32 position one add away from p.  At the volume's edge the sampler clamps: the gradient there is one-sided at
+ *              half magnitude.
+ *   world      texture_to_world, column-major, affine: linear part A, translation t.  x = A p + t, N = normalize(A^-T g),
+ *              V = -normalize(A dir) (dir: the ray's texture-space direction, in camera and buffer mode alike),
+ *              L = normalize(light_position - x), H = normalize(L + V), R = 2 (N.L) N - L.  normalize(0) = 0.
+ *   terms      ambient ka * c; diffuse kd * c |N.L|; Blinn specular ks |N.H|^s; Phong specular ks max(R.V, 0)^s (s = shininess).  The
+ *              absolute values make the shading two-sided: it does not change under N -> -N.
+ *   modes      AMBIENT: ambient; DIFFUSE: ambient + diffuse; SPECULAR: ambient + Phong specular; BLINN_PHONG: ambient + diffuse +
+ *              Blinn specular; PHONG: ambient + diffuse + Phong specular; NONE: c stays.
+ *   g = 0      all three components exactly +-0 (decided before the matrix): the diffuse and specular terms are 0.
+ * shading == NULL or mode NONE: cpm_render_ex with the same options -- the same kernels, the same bits; the other members are then not
+ * looked at.  With an accel a shaded image has the bits of the shaded image without one (a skipped sample has alpha 0 and is never shaded);
+ * stats count as in cpm_render_ex.
+ * Refused with CPM_ERR_INVALID_ARGUMENT, nothing written: whatever cpm_render_ex refuses; an unknown mode; a light position, colour or
+ * matrix element that is not finite; shininess <= 0 or not finite; a texture_to_world whose last row is not (0, 0, 0, 1) or whose linear
+ * part is singular. */
+typedef enum cpm_shade_mode {
+    CPM_SHADE_NONE = 0,
+    CPM_SHADE_AMBIENT = 1,
+    CPM_SHADE_DIFFUSE = 2,
+    CPM_SHADE_SPECULAR = 3,
+    CPM_SHADE_BLINN_PHONG = 4,
+    CPM_SHADE_PHONG = 5
+} cpm_shade_mode;
+typedef struct cpm_render_shading {
+    int32_t mode;               /* cpm_shade_mode */
+    float texture_to_world[16]; /* column-major, affine: the volume's world * model matrix */
+    float light_position[3];    /* world space */
+    float ambient[3];           /* ka */
+    float diffuse[3];           /* kd */
+    float specular[3];          /* ks */
+    float shininess;            /* s > 0 */
+} cpm_render_shading;
+
+int cpm_render_shaded(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const float* light_volume, const cpm_grid_desc* grid,
+                      const cpm_render_desc* desc, const cpm_render_options* options, const cpm_render_shading* shading, float* rgba_out,
+                      cpm_stream stream);
 
 #ifdef __cplusplus
 }
