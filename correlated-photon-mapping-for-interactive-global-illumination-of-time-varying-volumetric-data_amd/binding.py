@@ -17,7 +17,7 @@ _PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = _PKG_DIR / "libcpm_hip.so"
 
 CPM_OK = 0
-CPM_U8, CPM_U16, CPM_F32, CPM_F16 = 0, 1, 2, 3
+CPM_U8, CPM_U16, CPM_F32, CPM_F16, CPM_I16 = 0, 1, 2, 3, 4
 CPM_TRACE_PROGRESSIVE = 1
 CPM_TRACE_NO_SINGLE_SCATTERING = 2
 CPM_TRACE_PHOTONS_PLANAR = 4
@@ -534,15 +534,27 @@ def _f4(v):
 _TORCH_DTYPES = None
 
 
-def _dtype_code(t):
+def _dtype_code(t, dtype=None):
+    """cpm_dtype of a torch voxel tensor.  torch.int16 means u16 (the bits of a uint16 volume, from when torch had no uint16) unless
+    dtype=CPM_I16 says that the tensor holds signed voxels; any other explicit dtype must be the tensor's own."""
     import torch
-    return {torch.uint8: CPM_U8, torch.uint16: CPM_U16, torch.int16: CPM_U16, torch.float32: CPM_F32, torch.float16: CPM_F16}[t.dtype]
+    code = {torch.uint8: CPM_U8, torch.uint16: CPM_U16, torch.int16: CPM_U16, torch.float32: CPM_F32, torch.float16: CPM_F16}[t.dtype]
+    if dtype is None or int(dtype) == code:
+        return code
+    if int(dtype) == CPM_I16 and t.dtype == torch.int16:
+        return CPM_I16
+    raise ValueError(f"dtype={dtype} does not describe a {t.dtype} tensor")
 
 
 def _np_dtype_code(dtype):
-    """cpm_dtype of a numpy voxel type (float16: IEEE binary16, CPM_F16)."""
+    """cpm_dtype of a numpy voxel type (float16: IEEE binary16, CPM_F16; int16: signed normalised, CPM_I16)."""
     import numpy as np
-    return {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32, np.dtype(np.float16): CPM_F16}[np.dtype(dtype)]
+    return {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32, np.dtype(np.float16): CPM_F16,
+            np.dtype(np.int16): CPM_I16}[np.dtype(dtype)]
+
+
+# bytes per voxel of a cpm_dtype
+DTYPE_SIZE = {CPM_U8: 1, CPM_U16: 2, CPM_F32: 4, CPM_F16: 2, CPM_I16: 2}
 
 
 class Context:
@@ -618,16 +630,19 @@ class Context:
         return out
 
     # -- volume / tf
-    def volume_create(self, voxels, desc: VolumeDesc | None = None):
-        """voxels: torch tensor [z, y, x] (u8 / u16-as-int16|uint16 / f32 / f16) on the GPU, or a numpy array on the host."""
+    def volume_create(self, voxels, desc: VolumeDesc | None = None, dtype=None):
+        """voxels: torch tensor [z, y, x] (u8 / u16-as-int16|uint16 / f32 / f16) on the GPU, or a numpy array on the host (the same types,
+        and int16 = CPM_I16).  dtype=CPM_I16 makes a torch.int16 tensor a signed volume; without it the tensor stays u16."""
         import numpy as np
         if isinstance(voxels, np.ndarray):
             code = _np_dtype_code(voxels.dtype)
+            if dtype is not None and int(dtype) != code:
+                raise ValueError(f"dtype={dtype} does not describe a {voxels.dtype} array")
             dims = voxels.shape[::-1]
             voxels = np.ascontiguousarray(voxels)
             ptr, is_dev = C.c_void_p(voxels.ctypes.data), 0
         else:
-            code = _dtype_code(voxels)
+            code = _dtype_code(voxels, dtype)
             dims = tuple(voxels.shape[::-1])
             ptr, is_dev = self._ptr(voxels), 1
         if desc is None:
@@ -1353,7 +1368,7 @@ class Volume:
     def download(self):
         """Voxels as a numpy array [z, y, x] (blocking device -> host copy)."""
         import numpy as np
-        dt = {CPM_U8: np.uint8, CPM_U16: np.uint16, CPM_F32: np.float32, CPM_F16: np.float16}[int(self.desc.dtype)]
+        dt = {CPM_U8: np.uint8, CPM_U16: np.uint16, CPM_F32: np.float32, CPM_F16: np.float16, CPM_I16: np.int16}[int(self.desc.dtype)]
         out = np.empty(tuple(self.desc.dims)[::-1], dtype=dt)
         self.ctx._check(self.ctx.lib.cpm_volume_download(self.ctx.h, self.h, C.c_void_p(out.ctypes.data), self.ctx._stream()))
         return out

@@ -22,6 +22,7 @@ CPM_DEV float raw_voxel(const void* v, int dtype, size_t idx) {
     if (dtype == CPM_U8) return (float)static_cast<const uint8_t*>(v)[idx];
     if (dtype == CPM_U16) return (float)static_cast<const uint16_t*>(v)[idx];
     if (dtype == CPM_F16) return half_to_float(static_cast<const uint16_t*>(v)[idx]);
+    if (dtype == CPM_I16) return snorm16_to_float(static_cast<const uint16_t*>(v)[idx]);
     return static_cast<const float*>(v)[idx];
 }
 
@@ -58,8 +59,8 @@ __global__ __launch_bounds__(64) void minmax_kernel(BrickVol V, uint16_t* __rest
 
 // VolumeRAMDifferenceAnalysisDispatcher (ref uniformgridcl/processors/dynamicvolumedifferenceanalysis.h:96-151):
 // mean |b - a| per brick over the format's range; integer formats sum exactly (u64),
-// float volumes are summed by one lane in the reference's x-y-z order (double) -- binary16 ones over their widened values, so
-// that they give the F32 volume's bits.
+// float volumes are summed by one lane in the reference's x-y-z order (double) -- binary16 and int16 (SNORM) ones over their widened
+// values, so that they give the F32 volume's bits.
 __global__ __launch_bounds__(64) void difference_kernel(BrickVol A, const void* __restrict__ bvox, double range,
                                                         float* __restrict__ out) {
     const int brick = blockIdx.x;
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(64) void difference_kernel(BrickVol A, const void* 
     const int x0 = gx * A.region, y0 = gy * A.region, z0 = gz * A.region;
     const int ex = min(x0 + A.region, A.dx), ey = min(y0 + A.region, A.dy), ez = min(z0 + A.region, A.dz);
     const double cnt = (double)A.region * A.region * A.region;
-    if (A.dtype == CPM_F32 || A.dtype == CPM_F16) {
+    if (A.dtype == CPM_F32 || A.dtype == CPM_F16 || A.dtype == CPM_I16) {
         if (threadIdx.x != 0) return;
         double sum = 0;
         for (int z = z0; z < ez; ++z)
@@ -235,8 +236,9 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
     }
 }
 
-// rows must start on 16-byte boundaries for the vector loads (hipMalloc aligns the block itself)
-bool rows_are_16_byte_aligned(const BrickVol& V) {
+// rows must start on 16-byte boundaries for the vector loads (hipMalloc aligns the block itself), and the type needs an instantiation
+bool row_kernel_applies(const BrickVol& V) {
+    if (V.dtype == CPM_I16) return false;  // int16 keeps the per-brick kernels (raw_voxel widens with w(v)): no row kernel is instantiated for it
     const int es = V.dtype == CPM_U8 ? 1 : (V.dtype == CPM_U16 || V.dtype == CPM_F16 ? 2 : 4);
     return ((size_t)V.dx * es) % 16 == 0;
 }
@@ -854,7 +856,7 @@ int make_brick_vol(cpm_ctx* ctx, const cpm_volume* vol, int region, BrickVol& V)
     V.dx = d.dims[0]; V.dy = d.dims[1]; V.dz = d.dims[2]; V.dtype = d.dtype;
     V.region = region;
     V.ox = (V.dx + region - 1) / region; V.oy = (V.dy + region - 1) / region; V.oz = (V.dz + region - 1) / region;
-    V.norm = d.dtype == CPM_U8 ? (1.0f / 255.0f) : (d.dtype == CPM_U16 ? (1.0f / 65535.0f) : 1.0f);
+    V.norm = d.dtype == CPM_U8 ? (1.0f / 255.0f) : (d.dtype == CPM_U16 ? (1.0f / 65535.0f) : 1.0f);  // (F16, F32, I16: 1)
     V.offset = d.format_offset;
     V.one_minus_scaling = 1.0f - d.format_scaling;
     return CPM_OK;
@@ -876,7 +878,7 @@ int cpm_volume_minmax(cpm_ctx* ctx, const cpm_volume* vol, int region, uint16_t*
     if (rc) return rc;
     CPM_REQUIRE(ctx, minmax2, "cpm_volume_minmax: null output");
     hipStream_t s = (hipStream_t)stream;
-    if (ctx->dbg.brick_streaming && rows_are_16_byte_aligned(V) && (size_t)V.ox * 8 <= 48 * 1024) {
+    if (ctx->dbg.brick_streaming && row_kernel_applies(V) && (size_t)V.ox * 8 <= 48 * 1024) {
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
         const size_t lds = (size_t)V.ox * 8;
         switch (V.dtype) {
@@ -904,7 +906,7 @@ int cpm_volume_difference(cpm_ctx* ctx, const cpm_volume* cur, const cpm_volume*
                 "cpm_volume_difference: volumes differ in shape or type");
     double range = V.dtype == CPM_U8 ? 255.0 : (V.dtype == CPM_U16 ? 65535.0 : 1.0);
     if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && (V.dtype != CPM_F16 || region <= kHalfMaxStreamRegion) &&
-        rows_are_16_byte_aligned(V) && (size_t)V.ox * 8 <= 48 * 1024) {
+        row_kernel_applies(V) && (size_t)V.ox * 8 <= 48 * 1024) {
         // (f32 volumes keep the per-brick kernel: their sum is defined in the reference's x-y-z order in double; f16 ones take
         // the streaming kernel only where that double sum is exact -- region <= 16 -- and so order-free)
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
@@ -931,7 +933,7 @@ int cpm_volume_step(cpm_ctx* ctx, const cpm_volume* cur, const cpm_volume* next,
     CPM_REQUIRE(ctx, memcmp(cur->desc.dims, next->desc.dims, sizeof(cur->desc.dims)) == 0 && cur->desc.dtype == next->desc.dtype,
                 "cpm_volume_step: volumes differ in shape or type");
     if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && (V.dtype != CPM_F16 || region <= kHalfMaxStreamRegion) &&
-        rows_are_16_byte_aligned(V) && (size_t)V.ox * 16 <= 48 * 1024 &&
+        row_kernel_applies(V) && (size_t)V.ox * 16 <= 48 * 1024 &&
         cur->desc.format_offset == next->desc.format_offset && cur->desc.format_scaling == next->desc.format_scaling) {
         const double range = V.dtype == CPM_U8 ? 255.0 : (V.dtype == CPM_U16 ? 65535.0 : 1.0);
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
@@ -1455,6 +1457,7 @@ int retrace_impl(cpm_ctx* ctx, cpm_selection* s, const float* importance_grid, c
         case CPM_U8: CPM_RETRACE_LAUNCH(CPM_U8); break;
         case CPM_U16: CPM_RETRACE_LAUNCH(CPM_U16); break;
         case CPM_F16: CPM_RETRACE_LAUNCH(CPM_F16); break;
+        case CPM_I16: CPM_RETRACE_LAUNCH(CPM_I16); break;
         default: CPM_RETRACE_LAUNCH(CPM_F32); break;
     }
 #undef CPM_RETRACE_LAUNCH_L

@@ -29,6 +29,13 @@ CPM_DEV float lerp_(float x, float y, float a) { return fma_(a, y, fma_(-a, x, x
 // CPM_F16 voxels: the exact widening of an IEEE binary16 (the low 16 bits of h) to binary32 -- one v_cvt_f32_f16 (subnormals
 // included: every binary16 is a normal or zero binary32)
 CPM_DEV float half_to_float(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }
+// CPM_I16 voxels: w(v) of cpm.h for the int16 in the low 16 bits of h -- sign-extend, clamp -32768 to -32767, one v_cvt_f32_i32 and one
+// v_mul_f32 by fl32(1 / 32767) = 0x1.0002p-15 (a multiply in its own right: nothing here is contracted); w(+-32767) = +-1 exactly
+// (32767 * 0x1.0002p-15 = 1 - 2^-30, which rounds to 1)
+CPM_DEV float snorm16_to_float(uint32_t h) {
+    const int v = (int)(int16_t)(uint16_t)h;
+    return (float)(v < -32767 ? -32767 : v) * (1.0f / 32767.0f);
+}
 
 // natural log, x in [0, inf) normal; log(0) = -inf
 CPM_DEV float log_(float x) {

@@ -474,6 +474,7 @@ int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const floa
         case CPM_U8: CPM_RENDER_LAUNCH(CPM_U8); break;
         case CPM_U16: CPM_RENDER_LAUNCH(CPM_U16); break;
         case CPM_F16: CPM_RENDER_LAUNCH(CPM_F16); break;
+        case CPM_I16: CPM_RENDER_LAUNCH(CPM_I16); break;
         default: CPM_RENDER_LAUNCH(CPM_F32); break;
     }
 #undef CPM_RENDER_LAUNCH
@@ -604,6 +605,7 @@ static int render_ex_impl(cpm_ctx* ctx, const char* who, const cpm_volume* vol, 
         case CPM_U8: CPM_RENDER_EX_LAUNCH(CPM_U8); break;
         case CPM_U16: CPM_RENDER_EX_LAUNCH(CPM_U16); break;
         case CPM_F16: CPM_RENDER_EX_LAUNCH(CPM_F16); break;
+        case CPM_I16: CPM_RENDER_EX_LAUNCH(CPM_I16); break;
         default: CPM_RENDER_EX_LAUNCH(CPM_F32); break;
     }
 #undef CPM_RENDER_EX_LAUNCH

@@ -114,7 +114,7 @@ int cpm_render_accel_create(cpm_ctx* ctx, const cpm_volume_desc* desc, int brick
     if (brick <= 0) brick = 8;
     CPM_REQUIRE(ctx, brick == 4 || brick == 8 || brick == 16, "cpm_render_accel_create: brick must be 4, 8 or 16");
     CPM_REQUIRE(ctx, desc->dims[0] > 0 && desc->dims[1] > 0 && desc->dims[2] > 0, "cpm_render_accel_create: dims must be positive");
-    CPM_REQUIRE(ctx, desc->dtype == CPM_U8 || desc->dtype == CPM_U16 || desc->dtype == CPM_F16 || desc->dtype == CPM_F32,
+    CPM_REQUIRE(ctx, desc->dtype == CPM_U8 || desc->dtype == CPM_U16 || desc->dtype == CPM_F16 || desc->dtype == CPM_F32 || desc->dtype == CPM_I16,
                 "cpm_render_accel_create: unknown voxel type");
     CPM_REQUIRE(ctx, (unsigned long long)desc->dims[0] * desc->dims[1] * desc->dims[2] < (1ull << 32), "cpm_render_accel_create: volume too large");
     cpm_render_accel* a = new cpm_render_accel();
@@ -180,6 +180,7 @@ int cpm_render_accel_update(cpm_ctx* ctx, cpm_render_accel* accel, const cpm_vol
             case CPM_U8: CPM_RANGE_LAUNCH(CPM_U8); break;
             case CPM_U16: CPM_RANGE_LAUNCH(CPM_U16); break;
             case CPM_F16: CPM_RANGE_LAUNCH(CPM_F16); break;
+            case CPM_I16: CPM_RANGE_LAUNCH(CPM_I16); break;  // (w(v) is finite: never `bad`)
             default: CPM_RANGE_LAUNCH(CPM_F32); break;
         }
 #undef CPM_RANGE_LAUNCH

@@ -91,6 +91,16 @@ CPM_DEV uint32_t mix_f16_half(uint32_t x, uint32_t y, float a, float oma) {
 CPM_DEV uint32_t mix_f16_word(uint32_t x, uint32_t y, float a, float oma) {
     return mix_f16_half(x, y, a, oma) | (mix_f16_half(x >> 16, y >> 16, a, oma) << 16);
 }
+// int16 (SNORM): both texels normalised (w of cpm.h), the f32 branch's mix, then GL's SNORM write conversion
+// (int16) rint(clamp(m, -1, 1) * 32767), nearest even -- the F32 result of the widened volumes, converted (m is never NaN)
+CPM_DEV uint32_t mix_i16_half(uint32_t x, uint32_t y, float a, float oma) {
+    float m = mix_glsl(snorm16_to_float(x), snorm16_to_float(y), a, oma);
+    m = min_(max_(m, -1.0f), 1.0f);
+    return (uint32_t)(int)__builtin_rintf(m * 32767.0f) & 0xffffu;
+}
+CPM_DEV uint32_t mix_i16_word(uint32_t x, uint32_t y, float a, float oma) {
+    return mix_i16_half(x, y, a, oma) | (mix_i16_half(x >> 16, y >> 16, a, oma) << 16);
+}
 
 // volumes are allocated with a 16-byte tail pad (cpm_volume_create), so whole uint4 words cover them
 template <int DT>
@@ -114,6 +124,9 @@ __global__ __launch_bounds__(256) void volume_mix_kernel(const uint4* __restrict
         } else if (DT == CPM_F16) {
             r = make_uint4(mix_f16_word(p.x, q.x, a, oma), mix_f16_word(p.y, q.y, a, oma), mix_f16_word(p.z, q.z, a, oma),
                            mix_f16_word(p.w, q.w, a, oma));
+        } else if (DT == CPM_I16) {
+            r = make_uint4(mix_i16_word(p.x, q.x, a, oma), mix_i16_word(p.y, q.y, a, oma), mix_i16_word(p.z, q.z, a, oma),
+                           mix_i16_word(p.w, q.w, a, oma));
         } else {
             r = make_uint4(__float_as_uint(mix_glsl(__uint_as_float(p.x), __uint_as_float(q.x), a, oma)),
                            __float_as_uint(mix_glsl(__uint_as_float(p.y), __uint_as_float(q.y), a, oma)),
@@ -180,6 +193,7 @@ int cpm_volume_mix(cpm_ctx* ctx, const cpm_volume* v0, const cpm_volume* v1, flo
         case CPM_U8: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_U8>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
         case CPM_U16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_U16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
         case CPM_F16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_F16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
+        case CPM_I16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_I16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
         default: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_F32>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
     }
     CPM_LAUNCH_CHECK(ctx, "volume_mix_kernel");

@@ -102,6 +102,19 @@ template <> struct FootprintLoad<CPM_F16> {
         }
     }
 };
+// int16 (SNORM): the same 2-byte footprint, each texel normalised on its own (snorm16_to_float: v_bfe_i32 / v_ashrrev, v_max_i32,
+// v_cvt_f32_i32, v_mul_f32) before the f32 path's lerps -- a sample is the bits of the F32 volume of the normalised values
+template <> struct FootprintLoad<CPM_I16> {
+    static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
+        uint32_t w[4];
+        __builtin_memcpy(w, static_cast<const uint16_t*>(base) + 4 * (size_t)idx, 16);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i + 0] = snorm16_to_float(w[i]);
+            v[2 * i + 1] = snorm16_to_float(w[i] >> 16);
+        }
+    }
+};
 template <> struct FootprintLoad<CPM_F32> {
     static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
         __builtin_memcpy(v, static_cast<const float*>(base) + 4 * (size_t)idx, 32);
@@ -121,8 +134,8 @@ CPM_DEV void coord(float s, float dimf, float m1, float m2, float& fl, float& a)
 // with y' = min(y + 1, dim.y - 1), z' likewise -- exactly what a footprint element holds -- into the same order.
 template <int DT> struct LinearLoad {
     typedef typename std::conditional<DT == CPM_U8, uint8_t,
-            typename std::conditional<DT == CPM_U16 || DT == CPM_F16, uint16_t, float>::type>::type T;
-    static CPM_DEV float widen(T t) { return DT == CPM_F16 ? half_to_float(t) : (float)t; }
+            typename std::conditional<DT == CPM_U16 || DT == CPM_F16 || DT == CPM_I16, uint16_t, float>::type>::type T;
+    static CPM_DEV float widen(T t) { return DT == CPM_F16 ? half_to_float(t) : DT == CPM_I16 ? snorm16_to_float(t) : (float)t; }
     static CPM_DEV void load(const VolDev& V, uint32_t b00, int iy, int iz, float (&v)[8]) {
         const T* base = static_cast<const T*>(V.voxels) + b00;
         const uint32_t up = (float)iy < V.my1 ? V.sy : 0u, back = (float)iz < V.mz1 ? V.sz : 0u;

@@ -90,6 +90,14 @@ cpmh_network* cpmh_create(const void* voxels, int dtype, int dx, int dy, int dz,
 
 void cpmh_destroy(cpmh_network* net) { delete net; }
 
+// The volume's formatOffset / formatScaling where the type's default pair is not the data's range (a CT series in INT16; a FLOAT32 volume
+// holding normalised INT16 values).  Before the first evaluation: the volume is uploaded with it.
+int cpmh_set_volume_format_mapping(cpmh_network* net, float format_offset, float format_scaling) {
+    if (!net || !net->volume) return -1;
+    net->volume->setFormatMapping(format_offset, format_scaling);
+    return 0;
+}
+
 // One more directional light feeding the tracer's multi-inport (one tracer launch per light, photonOffset = the photons of the
 // lights before it: progressivephotontracercl.cpp:481-527,543-549).  Before the first evaluation.  Returns the light's index.
 int cpmh_add_light(cpmh_network* net, const float light_position[3], const float light_direction[3]) {

@@ -678,8 +678,7 @@ cpm_volume* Volume::getDeviceRepresentation() const {
     auto& rt = CpmRuntime::get();
     if (!rt.valid()) return nullptr;
     cpm_volume_desc d;
-    const int32_t dims[3] = { (int32_t)dims_.x, (int32_t)dims_.y, (int32_t)dims_.z };
-    cpm_volume_desc_default(&d, dims, dtype_);
+    fillDesc(d);
     const size_t bytes = dims_.x * dims_.y * dims_.z * elementSize();
     const void* src = ramBytes.size() == bytes ? ramBytes.data() : nullptr;
     if (!rt.check(cpm_volume_create(rt.ctx(), &d, src, 0, rt.stream(), &dev_), "cpm_volume_create")) dev_ = nullptr;

@@ -344,6 +344,7 @@ void VolumeSequencePlayer::process() {
         outVolume_ = std::make_shared<Volume>(from->getDimensions(), from->dtype());  // device storage only
         outVolume_->setModelMatrix(from->getModelMatrix());
         outVolume_->setWorldMatrix(from->getWorldMatrix());
+        outVolume_->copyFormatMapping(*from);
     }
     cpm_volume *a = nullptr, *b = nullptr, *blended = outVolume_->getDeviceRepresentation();
     if (keepSequenceOnDevice_.get()) {
@@ -356,8 +357,7 @@ void VolumeSequencePlayer::process() {
         if (stream_ && (streamedSequence_ != sequence.get() || (delta_ != nullptr) != uploadChangesOnly_.get())) dropStream();
         if (!stream_) {
             cpm_volume_desc d;
-            const int32_t dims[3] = { (int32_t)from->getDimensions().x, (int32_t)from->getDimensions().y, (int32_t)from->getDimensions().z };
-            cpm_volume_desc_default(&d, dims, from->dtype());
+            from->fillDesc(d);
             if (!rt.check(cpm_volume_stream_create(rt.ctx(), &d, 3, &stream_), "cpm_volume_stream_create")) { stream_ = nullptr; return; }
             streamedSequence_ = sequence.get();
             for (const auto& v : *sequence)   // page-lock the elements' RAM once: a copy from pageable memory is staged and holds this thread

@@ -135,15 +135,25 @@ public:
     size3_t getDimensions() const { return dims_; }
     void setDimensions(size3_t d) { dims_ = d; data.setSize(0); invalidateDeviceRepresentation(); }
     int dtype() const { return dtype_; }
-    size_t elementSize() const { return dtype_ == CPM_U8 ? 1 : (dtype_ == CPM_U16 || dtype_ == CPM_F16 ? 2 : 4); }
+    size_t elementSize() const { return dtype_ == CPM_U8 ? 1 : (dtype_ == CPM_U16 || dtype_ == CPM_F16 || dtype_ == CPM_I16 ? 2 : 4); }
     // getDataFormat()->getString() of the scalar formats the path takes (cpm_dtype)
     const char* getDataFormatString() const {
-        return dtype_ == CPM_U8 ? "UINT8" : dtype_ == CPM_U16 ? "UINT16" : dtype_ == CPM_F16 ? "FLOAT16" : "FLOAT32";
+        return dtype_ == CPM_U8 ? "UINT8" : dtype_ == CPM_U16 ? "UINT16" : dtype_ == CPM_F16 ? "FLOAT16" : dtype_ == CPM_I16 ? "INT16" : "FLOAT32";
     }
     const mat4& getModelMatrix() const { return model_; }
     const mat4& getWorldMatrix() const { return world_; }
     void setModelMatrix(const mat4& m) { model_ = m; }
     void setWorldMatrix(const mat4& m) { world_ = m; }
+    // VolumeParameters::formatOffset / formatScaling (what the DataMapper's ranges come to): the type's default pair
+    // (cpm_volume_desc_default -- INT16: 1, 0.5) until a data range sets its own; the device representation is rebuilt with it
+    void setFormatMapping(float offset, float scaling) { mapped_ = true; formatOffset_ = offset; formatScaling_ = scaling; invalidateDeviceRepresentation(); }
+    void copyFormatMapping(const Volume& o) { if (o.mapped_) setFormatMapping(o.formatOffset_, o.formatScaling_); }
+    // the cpm_volume_desc of this volume: dims, type, default matrices and the mapping above
+    void fillDesc(cpm_volume_desc& d) const {
+        const int32_t dims[3] = { (int32_t)dims_.x, (int32_t)dims_.y, (int32_t)dims_.z };
+        cpm_volume_desc_default(&d, dims, dtype_);
+        if (mapped_) { d.format_offset = formatOffset_; d.format_scaling = formatScaling_; }
+    }
     int channels = 1;               // light volumes: 1 (float32) or 4 (4xfloat32)
     std::vector<uint8_t> ramBytes;  // scalar source volumes live here until uploaded
     Buffer<float> data;             // light volumes: device float storage
@@ -157,6 +167,8 @@ public:
 private:
     size3_t dims_;
     int dtype_;
+    bool mapped_ = false;
+    float formatOffset_ = 0.f, formatScaling_ = 0.f;
     mat4 model_ = identityMatrix(), world_ = identityMatrix();
     mutable ::cpm_volume* dev_ = nullptr;
 };

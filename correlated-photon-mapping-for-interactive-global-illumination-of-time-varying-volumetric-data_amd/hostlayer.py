@@ -63,7 +63,7 @@ def load():
 
 class HostNetwork:
     """The CorrelatedPhotonMappingSingleVolume network in C++ (sample generator -> light sampler -> tracer -> light volume,
-    min/max -> importance -> tracer): cpmh_create's wiring.  The volume's numpy type picks the format (uint8, uint16, float32, float16)."""
+    min/max -> importance -> tracer): cpmh_create's wiring.  The volume's numpy type picks the format (uint8, uint16, float32, float16, int16)."""
 
     def __init__(self, lib, volume_u8, n_side, light_position, light_direction, tf_points, size_option=2, max_scattering=1,
                  correlated=True):

@@ -115,14 +115,16 @@ class PhotonFrame:
                  radiance=(1.0, 1.0, 1.0), radius_voxels: float = 1.0, max_interactions: int = 1,
                  channels: int = 1, photon_range=None, point_light_position=None, seed: int = 0,
                  shading_type: int = B.CPM_PHASE_HENYEY_GREENSTEIN, material=(0.0, 0.0, 0.0, 0.0), light_plane=None,
-                 mesh_intersection=None, emit_in_tracer: bool = False, photon_indices=None, records_layout=None):
+                 mesh_intersection=None, emit_in_tracer: bool = False, photon_indices=None, records_layout=None, volume_dtype=None):
+        """volume_dtype: the cpm_dtype of `volume` where its own type does not say it (B.CPM_I16 for a torch.int16 tensor of signed
+        voxels; without it such a tensor is u16)."""
         torch = ctx.torch
         self.ctx = ctx
         self.records_layout = records_layout
         self.torch = torch
         dev = ctx.device
         self._vol_is_own = not isinstance(volume, B.Volume)   # created here (set_volume may recycle it) or the caller's
-        self.vol = volume if isinstance(volume, B.Volume) else ctx.volume_create(volume)
+        self.vol = volume if isinstance(volume, B.Volume) else ctx.volume_create(volume, dtype=volume_dtype)
         self.tf = tf_rgba if isinstance(tf_rgba, B.TransferFunction) else ctx.tf_create(tf_rgba)
         nx, ny = (n_side, n_side) if isinstance(n_side, int) else n_side
         self.n_total = nx * ny
@@ -596,7 +598,10 @@ class CorrelatedPhotonMapper(PhotonFrame):
                 raise ValueError("set_volume: the time step differs from the current volume in shape or type")
             nxt = voxels
         elif self._vol_next is None:
-            nxt = ctx.volume_create(voxels)
+            if int(self.vol.desc.dtype) == B.CPM_I16:  # signed voxels keep the current volume's type (a torch.int16 tensor alone
+                nxt = ctx.volume_create(voxels, desc=self.vol.desc, dtype=B.CPM_I16)  # would be u16) and its offset / scaling
+            else:
+                nxt = ctx.volume_create(voxels)
         else:
             nxt = self._vol_next
             nxt.update(voxels)

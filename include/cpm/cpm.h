@@ -109,7 +109,20 @@ int cpm_random_fill(cpm_ctx* ctx, uint32_t* state, size_t n, int draws, float* o
  * min/max and difference bricks, importance, selections, light volumes; where the result is itself a volume (cpm_volume_mix)
  * it is the f32 result rounded to nearest even.  (Min/max bricks: NaN voxels are ignored, as the per-brick f32 form ignores
  * them; difference bricks: a NaN term makes the brick NaN, else an inf term makes it inf -- the f32 path's double sum.) */
-typedef enum cpm_dtype { CPM_U8 = 0, CPM_U16 = 1, CPM_F32 = 2, CPM_F16 = 3 } cpm_dtype;
+typedef enum cpm_dtype { CPM_U8 = 0, CPM_U16 = 1, CPM_F32 = 2, CPM_F16 = 3, CPM_I16 = 4 } cpm_dtype;
+/* CPM_I16: two's-complement 16-bit voxels, x fastest.  A voxel's value is what an OpenCL CL_SNORM_INT16 image returns for the texel,
+ * normalised before any filtering:
+ *     w(v) = fl32( (float)max(v, -32767) * fl32(1.0f / 32767.0f) )     (one convert, one multiply; -32768 and -32767 both give -1)
+ * fl32(1 / 32767) = 0x1.0002p-15 (rounded down), 32767 times it is 1 - 2^-30, and that rounds to w(32767) = 1.0f exactly (w(-32767) = -1.0f).  From w on the voxel is mapped like an
+ * f32 voxel ((w + format_offset) * (1 - format_scaling), norm 1); a trilinear sample widens its 8 texels with w and uses the f32
+ * path's lerps.  cpm_volume_desc_default sets format_offset = 1, format_scaling = 0.5 for I16 (the type's range onto [0, 1]: assumed
+ * from Inviwo's signed normalised formats, not checked against an Inviwo); a caller with a data range sets its own pair (CT,
+ * -1024..3071: offset 1024 / 32767, 1 - scaling = 32767 / 4095).  Invariant: every operation on an I16 volume gives the bits the same
+ * operation gives on the F32 volume holding w(v) under the same format_offset / format_scaling -- photons, RNG states, min/max and
+ * difference bricks, cpm_volume_step, importance, selections, fused and budgeted updates, light volumes, rendered images (with or
+ * without an accel, shaded or not).  Where the result is itself a volume (cpm_volume_mix), with m the f32 path's mix of the widened
+ * values: out = (int16) rintf(clamp(m, -1, 1) * 32767.0f), round to nearest even (GL's SNORM write conversion).
+ * CPM_ABI_VERSION stays 2, as it did for CPM_F16: the enum grows, no struct or entry point changes. */
 
 /* Mirrors the fields of Inviwo's VolumeParameters the path reads
  * (ref use sites progressivephotonmapping/cl/photontracer.cl:75,
@@ -119,8 +132,8 @@ typedef enum cpm_dtype { CPM_U8 = 0, CPM_U16 = 1, CPM_F32 = 2, CPM_F16 = 3 } cpm
 typedef struct cpm_volume_desc {
     int32_t dims[3];
     int32_t dtype;          /* cpm_dtype */
-    float format_scaling;   /* VolumeParameters::formatScaling (0 for 8/16-bit UNORM, float) */
-    float format_offset;    /* VolumeParameters::formatOffset */
+    float format_scaling;   /* VolumeParameters::formatScaling (0 for 8/16-bit UNORM, float; 0.5 for I16) */
+    float format_offset;    /* VolumeParameters::formatOffset (1 for I16) */
     float texture_to_index[16];
     float index_to_texture[16];
 } cpm_volume_desc;
