@@ -18,6 +18,12 @@ LIB_PATH = _PKG_DIR / "libcpm_hip.so"
 
 CPM_OK = 0
 CPM_U8, CPM_U16, CPM_F32, CPM_F16, CPM_I16 = 0, 1, 2, 3, 4
+#: one row per voxel type: (cpm_dtype, numpy dtype name, torch dtype name or None, bytes per voxel).  I16 has no torch dtype of its own:
+#: a torch.int16 tensor is u16 unless the caller says dtype=CPM_I16 (_dtype_code)
+VOXEL_TYPES = ((CPM_U8, "uint8", "uint8", 1), (CPM_U16, "uint16", "uint16", 2), (CPM_F32, "float32", "float32", 4),
+               (CPM_F16, "float16", "float16", 2), (CPM_I16, "int16", None, 2))
+#: bytes per voxel of a cpm_dtype
+DTYPE_SIZE = {code: size for code, _, _, size in VOXEL_TYPES}
 CPM_TRACE_PROGRESSIVE = 1
 CPM_TRACE_NO_SINGLE_SCATTERING = 2
 CPM_TRACE_PHOTONS_PLANAR = 4
@@ -531,14 +537,13 @@ def _f4(v):
     return (C.c_float * 4)(*v[:4])
 
 
-_TORCH_DTYPES = None
-
-
 def _dtype_code(t, dtype=None):
     """cpm_dtype of a torch voxel tensor.  torch.int16 means u16 (the bits of a uint16 volume, from when torch had no uint16) unless
     dtype=CPM_I16 says that the tensor holds signed voxels; any other explicit dtype must be the tensor's own."""
     import torch
-    code = {torch.uint8: CPM_U8, torch.uint16: CPM_U16, torch.int16: CPM_U16, torch.float32: CPM_F32, torch.float16: CPM_F16}[t.dtype]
+    codes = {getattr(torch, name): code for code, _, name, _ in VOXEL_TYPES if name}
+    codes[torch.int16] = CPM_U16
+    code = codes[t.dtype]
     if dtype is None or int(dtype) == code:
         return code
     if int(dtype) == CPM_I16 and t.dtype == torch.int16:
@@ -549,12 +554,7 @@ def _dtype_code(t, dtype=None):
 def _np_dtype_code(dtype):
     """cpm_dtype of a numpy voxel type (float16: IEEE binary16, CPM_F16; int16: signed normalised, CPM_I16)."""
     import numpy as np
-    return {np.dtype(np.uint8): CPM_U8, np.dtype(np.uint16): CPM_U16, np.dtype(np.float32): CPM_F32, np.dtype(np.float16): CPM_F16,
-            np.dtype(np.int16): CPM_I16}[np.dtype(dtype)]
-
-
-# bytes per voxel of a cpm_dtype
-DTYPE_SIZE = {CPM_U8: 1, CPM_U16: 2, CPM_F32: 4, CPM_F16: 2, CPM_I16: 2}
+    return {np.dtype(name): code for code, name, _, _ in VOXEL_TYPES}[np.dtype(dtype)]
 
 
 class Context:
@@ -1368,7 +1368,7 @@ class Volume:
     def download(self):
         """Voxels as a numpy array [z, y, x] (blocking device -> host copy)."""
         import numpy as np
-        dt = {CPM_U8: np.uint8, CPM_U16: np.uint16, CPM_F32: np.float32, CPM_F16: np.float16, CPM_I16: np.int16}[int(self.desc.dtype)]
+        dt = {code: np.dtype(name) for code, name, _, _ in VOXEL_TYPES}[int(self.desc.dtype)]
         out = np.empty(tuple(self.desc.dims)[::-1], dtype=dt)
         self.ctx._check(self.ctx.lib.cpm_volume_download(self.ctx.h, self.h, C.c_void_p(out.ctypes.data), self.ctx._stream()))
         return out

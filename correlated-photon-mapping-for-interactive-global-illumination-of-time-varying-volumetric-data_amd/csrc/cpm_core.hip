@@ -109,12 +109,9 @@ static int launch_quads(cpm_ctx* ctx, cpm_volume* vol, const void* src, hipStrea
 namespace cpm {
 int build_quads(cpm_ctx* ctx, cpm_volume* vol, const void* src, bool copy_linear, hipStream_t s) {
     vol->quads_stale = false;
-    switch (vol->desc.dtype) {
-        case CPM_U8: return copy_linear ? launch_quads<uint8_t, true>(ctx, vol, src, s) : launch_quads<uint8_t, false>(ctx, vol, src, s);
-        case CPM_U16:
-        case CPM_F16:  // (a bit copy: binary16 moves as its 2 bytes)
-        case CPM_I16:  // (and so does int16: -32768 is clamped where a voxel is widened, not here)
-            return copy_linear ? launch_quads<uint16_t, true>(ctx, vol, src, s) : launch_quads<uint16_t, false>(ctx, vol, src, s);
+    switch (cpm_dtype_size(vol->desc.dtype)) {  // a bit copy: a voxel moves as its bytes (binary16 too; int16's -32768 is clamped where a voxel is widened, not here)
+        case 1: return copy_linear ? launch_quads<uint8_t, true>(ctx, vol, src, s) : launch_quads<uint8_t, false>(ctx, vol, src, s);
+        case 2: return copy_linear ? launch_quads<uint16_t, true>(ctx, vol, src, s) : launch_quads<uint16_t, false>(ctx, vol, src, s);
         default: return copy_linear ? launch_quads<uint32_t, true>(ctx, vol, src, s) : launch_quads<uint32_t, false>(ctx, vol, src, s);
     }
 }
@@ -273,9 +270,8 @@ void cpm_volume_desc_default(cpm_volume_desc* d, const int32_t dims[3], int32_t 
     memset(d, 0, sizeof(*d));
     for (int a = 0; a < 3; ++a) d->dims[a] = dims[a];
     d->dtype = dtype;
-    // I16 (SNORM): [-1, 1] -> [0, 1], as Inviwo maps signed normalised formats; every other type is used as it is
-    d->format_scaling = dtype == CPM_I16 ? 0.5f : 0.0f;
-    d->format_offset = dtype == CPM_I16 ? 1.0f : 0.0f;
+    d->format_scaling = dtype_default_scaling(dtype);
+    d->format_offset = dtype_default_offset(dtype);
     default_matrices(dims, d->texture_to_index, d->index_to_texture);
 }
 
@@ -292,14 +288,11 @@ float cpm_relative_irradiance_scale(double radius, double n_photons) {
     return (float)((1. / pi) / (vol * n_photons));
 }
 
-static size_t dtype_size(int dtype) { return dtype == CPM_U8 ? 1 : (dtype == CPM_U16 || dtype == CPM_F16 || dtype == CPM_I16 ? 2 : 4); }
-
-
 int cpm_volume_create(cpm_ctx* ctx, const cpm_volume_desc* desc, const void* voxels, int is_device,
                       cpm_stream stream, cpm_volume** out) {
     CPM_ENTER(ctx);
     CPM_REQUIRE(ctx, desc && out, "cpm_volume_create: null argument");
-    CPM_REQUIRE(ctx, desc->dtype >= CPM_U8 && desc->dtype <= CPM_I16, "cpm_volume_create: dtype");
+    CPM_REQUIRE(ctx, cpm_dtype_valid(desc->dtype), "cpm_volume_create: dtype");
     CPM_REQUIRE(ctx, desc->dims[0] >= 2 && desc->dims[1] >= 1 && desc->dims[2] >= 1, "cpm_volume_create: dims (x >= 2)");
     Affine a;
     if (!affine_from_matrix(desc->texture_to_index, a) || !affine_from_matrix(desc->index_to_texture, a))
@@ -307,7 +300,7 @@ int cpm_volume_create(cpm_ctx* ctx, const cpm_volume_desc* desc, const void* vox
     cpm_volume* v = new (std::nothrow) cpm_volume();
     if (!v) return set_error(ctx, CPM_ERR_OUT_OF_MEMORY, "cpm_volume_create", "host allocation failed");
     v->desc = *desc;
-    v->bytes = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2] * dtype_size(desc->dtype);
+    v->bytes = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2] * cpm_dtype_size(desc->dtype);
     hipError_t e = hipMalloc(&v->voxels, v->bytes + 16);  // tail pad: paired x loads never leave the allocation
     if (e != hipSuccess) { delete v; return set_error(ctx, CPM_ERR_OUT_OF_MEMORY, "hipMalloc(volume)", hipGetErrorString(e)); }
     e = hipMalloc(&v->quads, 4 * v->bytes + 64);

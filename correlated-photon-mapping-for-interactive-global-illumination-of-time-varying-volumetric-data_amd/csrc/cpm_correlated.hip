@@ -19,11 +19,9 @@ struct BrickVol {
 };
 
 CPM_DEV float raw_voxel(const void* v, int dtype, size_t idx) {
-    if (dtype == CPM_U8) return (float)static_cast<const uint8_t*>(v)[idx];
-    if (dtype == CPM_U16) return (float)static_cast<const uint16_t*>(v)[idx];
-    if (dtype == CPM_F16) return half_to_float(static_cast<const uint16_t*>(v)[idx]);
-    if (dtype == CPM_I16) return snorm16_to_float(static_cast<const uint16_t*>(v)[idx]);
-    return static_cast<const float*>(v)[idx];
+#define CPM_RAW_VOXEL(DT) return Voxel<DT>::widen(static_cast<const Voxel<DT>::T*>(v)[idx])
+    CPM_DISPATCH_DTYPE(dtype, CPM_RAW_VOXEL);
+#undef CPM_RAW_VOXEL
 }
 
 // volumeMinMaxKernel (ref uniformgridcl/cl/uniformgrid/volumeminmax.cl:33-61).  One wave per
@@ -142,7 +140,7 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
     extern __shared__ unsigned long long s_slots[];  // DIFF: ox sums; MINMAX: ox minima and ox maxima (u32) behind them
     uint32_t* s_min = reinterpret_cast<uint32_t*>(s_slots + (DIFF ? A.ox : 0));
     uint32_t* s_max = s_min + A.ox;
-    constexpr int ES = DT == CPM_U8 ? 1 : (DT == CPM_U16 || DT == CPM_F16 ? 2 : 4);
+    constexpr int ES = Voxel<DT>::size;
     constexpr int EPC = 16 / ES;  // elements per 16-byte chunk
     const int gy = blockIdx.x % A.oy, gz = blockIdx.x / A.oy;
     const int R = A.region;
@@ -173,8 +171,8 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
         for (int e = 0; e < EPC; ++e) {
             if (xb + e < A.dx) {
                 uint32_t va, vb = 0;
-                if (DT == CPM_U8) { va = (wa[e >> 2] >> (8 * (e & 3))) & 0xffu; vb = (wb[e >> 2] >> (8 * (e & 3))) & 0xffu; }
-                else if (DT == CPM_U16 || DT == CPM_F16) { va = (wa[e >> 1] >> (16 * (e & 1))) & 0xffffu; vb = (wb[e >> 1] >> (16 * (e & 1))) & 0xffffu; }
+                if (ES == 1) { va = (wa[e >> 2] >> (8 * (e & 3))) & 0xffu; vb = (wb[e >> 2] >> (8 * (e & 3))) & 0xffu; }
+                else if (ES == 2) { va = (wa[e >> 1] >> (16 * (e & 1))) & 0xffffu; vb = (wb[e >> 1] >> (16 * (e & 1))) & 0xffffu; }
                 else va = wa[e];
                 if (DT == CPM_F32) {  // (MODE 0)
                     if (!maps_to_nan(__uint_as_float(va), A)) { const uint32_t k = float_key(__uint_as_float(va)); mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
@@ -239,8 +237,7 @@ __global__ __launch_bounds__(256) void brick_row_kernel(BrickVol A, const void* 
 // rows must start on 16-byte boundaries for the vector loads (hipMalloc aligns the block itself), and the type needs an instantiation
 bool row_kernel_applies(const BrickVol& V) {
     if (V.dtype == CPM_I16) return false;  // int16 keeps the per-brick kernels (raw_voxel widens with w(v)): no row kernel is instantiated for it
-    const int es = V.dtype == CPM_U8 ? 1 : (V.dtype == CPM_U16 || V.dtype == CPM_F16 ? 2 : 4);
-    return ((size_t)V.dx * es) % 16 == 0;
+    return ((size_t)V.dx * cpm_dtype_size(V.dtype)) % 16 == 0;
 }
 
 CPM_DEV float4 mix4(float4 a, float4 b, float t) {
@@ -856,9 +853,7 @@ int make_brick_vol(cpm_ctx* ctx, const cpm_volume* vol, int region, BrickVol& V)
     V.dx = d.dims[0]; V.dy = d.dims[1]; V.dz = d.dims[2]; V.dtype = d.dtype;
     V.region = region;
     V.ox = (V.dx + region - 1) / region; V.oy = (V.dy + region - 1) / region; V.oz = (V.dz + region - 1) / region;
-    V.norm = d.dtype == CPM_U8 ? (1.0f / 255.0f) : (d.dtype == CPM_U16 ? (1.0f / 65535.0f) : 1.0f);  // (F16, F32, I16: 1)
-    V.offset = d.format_offset;
-    V.one_minus_scaling = 1.0f - d.format_scaling;
+    set_value_mapping(V, d);
     return CPM_OK;
 }
 
@@ -881,12 +876,10 @@ int cpm_volume_minmax(cpm_ctx* ctx, const cpm_volume* vol, int region, uint16_t*
     if (ctx->dbg.brick_streaming && row_kernel_applies(V) && (size_t)V.ox * 8 <= 48 * 1024) {
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
         const size_t lds = (size_t)V.ox * 8;
-        switch (V.dtype) {
-            case CPM_U8: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U8, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
-            case CPM_U16: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U16, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
-            case CPM_F16: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F16, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
-            default: CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F32, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr); break;
-        }
+#define CPM_ROW_MINMAX(DT) CPM_LAUNCH(ctx, (brick_row_kernel<DT, 0>), grid, block, lds, s, V, nullptr, 1.0, minmax2, nullptr)
+        if (V.dtype != CPM_F32) CPM_DISPATCH_DTYPE3(V.dtype, CPM_ROW_MINMAX, CPM_U8, CPM_U16, CPM_F16);  // (I16: row_kernel_applies)
+        else CPM_ROW_MINMAX(CPM_F32);  // (min / max only: the one row kernel an F32 volume has)
+#undef CPM_ROW_MINMAX
         CPM_LAUNCH_CHECK(ctx, "brick_row_kernel");
         return CPM_OK;
     }
@@ -904,7 +897,7 @@ int cpm_volume_difference(cpm_ctx* ctx, const cpm_volume* cur, const cpm_volume*
     CPM_REQUIRE(ctx, next && out, "cpm_volume_difference: null argument");
     CPM_REQUIRE(ctx, memcmp(cur->desc.dims, next->desc.dims, sizeof(cur->desc.dims)) == 0 && cur->desc.dtype == next->desc.dtype,
                 "cpm_volume_difference: volumes differ in shape or type");
-    double range = V.dtype == CPM_U8 ? 255.0 : (V.dtype == CPM_U16 ? 65535.0 : 1.0);
+    const double range = dtype_range(V.dtype);
     if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && (V.dtype != CPM_F16 || region <= kHalfMaxStreamRegion) &&
         row_kernel_applies(V) && (size_t)V.ox * 8 <= 48 * 1024) {
         // (f32 volumes keep the per-brick kernel: their sum is defined in the reference's x-y-z order in double; f16 ones take
@@ -912,9 +905,9 @@ int cpm_volume_difference(cpm_ctx* ctx, const cpm_volume* cur, const cpm_volume*
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
         const size_t lds = (size_t)V.ox * 8;
         hipStream_t s = (hipStream_t)stream;
-        if (V.dtype == CPM_U8) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U8, 1>), grid, block, lds, s, V, next->voxels, range, nullptr, out);
-        else if (V.dtype == CPM_F16) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F16, 1>), grid, block, lds, s, V, next->voxels, range, nullptr, out);
-        else CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U16, 1>), grid, block, lds, s, V, next->voxels, range, nullptr, out);
+#define CPM_ROW_DIFF(DT) CPM_LAUNCH(ctx, (brick_row_kernel<DT, 1>), grid, block, lds, s, V, next->voxels, range, nullptr, out)
+        CPM_DISPATCH_DTYPE3(V.dtype, CPM_ROW_DIFF, CPM_U8, CPM_F16, CPM_U16);
+#undef CPM_ROW_DIFF
         CPM_LAUNCH_CHECK(ctx, "brick_row_kernel");
         return CPM_OK;
     }
@@ -935,13 +928,13 @@ int cpm_volume_step(cpm_ctx* ctx, const cpm_volume* cur, const cpm_volume* next,
     if (ctx->dbg.brick_streaming && V.dtype != CPM_F32 && (V.dtype != CPM_F16 || region <= kHalfMaxStreamRegion) &&
         row_kernel_applies(V) && (size_t)V.ox * 16 <= 48 * 1024 &&
         cur->desc.format_offset == next->desc.format_offset && cur->desc.format_scaling == next->desc.format_scaling) {
-        const double range = V.dtype == CPM_U8 ? 255.0 : (V.dtype == CPM_U16 ? 65535.0 : 1.0);
+        const double range = dtype_range(V.dtype);
         const dim3 grid((unsigned)(V.oy * V.oz)), block(256);
         const size_t lds = (size_t)V.ox * 16;
         hipStream_t s = (hipStream_t)stream;
-        if (V.dtype == CPM_U8) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U8, 2>), grid, block, lds, s, V, next->voxels, range, next_minmax2, mean_abs_diff);
-        else if (V.dtype == CPM_F16) CPM_LAUNCH(ctx, (brick_row_kernel<CPM_F16, 2>), grid, block, lds, s, V, next->voxels, range, next_minmax2, mean_abs_diff);
-        else CPM_LAUNCH(ctx, (brick_row_kernel<CPM_U16, 2>), grid, block, lds, s, V, next->voxels, range, next_minmax2, mean_abs_diff);
+#define CPM_ROW_STEP(DT) CPM_LAUNCH(ctx, (brick_row_kernel<DT, 2>), grid, block, lds, s, V, next->voxels, range, next_minmax2, mean_abs_diff)
+        CPM_DISPATCH_DTYPE3(V.dtype, CPM_ROW_STEP, CPM_U8, CPM_F16, CPM_U16);
+#undef CPM_ROW_STEP
         CPM_LAUNCH_CHECK(ctx, "brick_row_kernel");
         return CPM_OK;
     }
@@ -1453,13 +1446,7 @@ int retrace_impl(cpm_ctx* ctx, cpm_selection* s, const float* importance_grid, c
         else if (linear) CPM_RETRACE_LAUNCH_L(DT, true);        \
         else CPM_RETRACE_LAUNCH_L(DT, false);                   \
     } while (0)
-    switch (vol->desc.dtype) {
-        case CPM_U8: CPM_RETRACE_LAUNCH(CPM_U8); break;
-        case CPM_U16: CPM_RETRACE_LAUNCH(CPM_U16); break;
-        case CPM_F16: CPM_RETRACE_LAUNCH(CPM_F16); break;
-        case CPM_I16: CPM_RETRACE_LAUNCH(CPM_I16); break;
-        default: CPM_RETRACE_LAUNCH(CPM_F32); break;
-    }
+    CPM_DISPATCH_DTYPE(vol->desc.dtype, CPM_RETRACE_LAUNCH);
 #undef CPM_RETRACE_LAUNCH_L
 #undef CPM_RETRACE_LAUNCH_M
 #undef CPM_RETRACE_LAUNCH

@@ -11,6 +11,7 @@
 
 #include "cpm/cpm_ext.h"
 #include "cpm_math.hip.h"
+#include "cpm_voxel.h"
 
 struct cpm_prof_record { const char* name; hipEvent_t a, b; };
 struct cpm_prof_entry { std::string name; double total_ms = 0; long calls = 0; };

@@ -23,12 +23,11 @@ constexpr int kMaxThreads = 16;   // the pre-pass's pool: a fixed cap, never the
 uint64_t round16(uint64_t n) { return (n + 15) & ~uint64_t(15); }
 
 size_t step_bytes_of(const cpm_volume_desc* d) {
-    const size_t es = d->dtype == CPM_U8 ? 1 : (d->dtype == CPM_U16 || d->dtype == CPM_F16 || d->dtype == CPM_I16 ? 2 : 4);
-    return (size_t)d->dims[0] * d->dims[1] * d->dims[2] * es;
+    return (size_t)d->dims[0] * d->dims[1] * d->dims[2] * cpm_dtype_size(d->dtype);
 }
 
 bool desc_ok(const cpm_volume_desc* d) {
-    return d && d->dtype >= CPM_U8 && d->dtype <= CPM_I16 && d->dims[0] >= 1 && d->dims[1] >= 1 && d->dims[2] >= 1 &&
+    return d && cpm_dtype_valid(d->dtype) && d->dims[0] >= 1 && d->dims[1] >= 1 && d->dims[2] >= 1 &&
            (uint64_t)d->dims[0] * d->dims[1] * d->dims[2] * 4 <= kPiece * 0xffffffffull;
 }
 

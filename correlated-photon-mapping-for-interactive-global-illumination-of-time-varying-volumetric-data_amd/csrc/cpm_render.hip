@@ -470,13 +470,7 @@ int cpm_render(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const floa
         if (grid->channels == 1) CPM_LAUNCH(ctx, (render_kernel<DT, 1>), g, b, lds, s, A);                  \
         else CPM_LAUNCH(ctx, (render_kernel<DT, 4>), g, b, lds, s, A);                                      \
     } while (0)
-    switch (vol->desc.dtype) {
-        case CPM_U8: CPM_RENDER_LAUNCH(CPM_U8); break;
-        case CPM_U16: CPM_RENDER_LAUNCH(CPM_U16); break;
-        case CPM_F16: CPM_RENDER_LAUNCH(CPM_F16); break;
-        case CPM_I16: CPM_RENDER_LAUNCH(CPM_I16); break;
-        default: CPM_RENDER_LAUNCH(CPM_F32); break;
-    }
+    CPM_DISPATCH_DTYPE(vol->desc.dtype, CPM_RENDER_LAUNCH);
 #undef CPM_RENDER_LAUNCH
     CPM_LAUNCH_CHECK(ctx, "render_kernel");
     return CPM_OK;
@@ -601,13 +595,7 @@ static int render_ex_impl(cpm_ctx* ctx, const char* who, const cpm_volume* vol, 
         if (grid->channels == 1) CPM_RENDER_EX_LAUNCH_M(DT, 1);                                             \
         else CPM_RENDER_EX_LAUNCH_M(DT, 4);                                                                 \
     } while (0)
-    switch (vol->desc.dtype) {
-        case CPM_U8: CPM_RENDER_EX_LAUNCH(CPM_U8); break;
-        case CPM_U16: CPM_RENDER_EX_LAUNCH(CPM_U16); break;
-        case CPM_F16: CPM_RENDER_EX_LAUNCH(CPM_F16); break;
-        case CPM_I16: CPM_RENDER_EX_LAUNCH(CPM_I16); break;
-        default: CPM_RENDER_EX_LAUNCH(CPM_F32); break;
-    }
+    CPM_DISPATCH_DTYPE(vol->desc.dtype, CPM_RENDER_EX_LAUNCH);
 #undef CPM_RENDER_EX_LAUNCH
 #undef CPM_RENDER_EX_LAUNCH_M
     CPM_LAUNCH_CHECK(ctx, mode & R_SHADE ? "render_shaded_kernel" : "render_ex_kernel");

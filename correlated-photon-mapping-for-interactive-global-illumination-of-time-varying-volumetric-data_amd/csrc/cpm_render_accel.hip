@@ -23,7 +23,7 @@ constexpr int kColumns = 256;
 template <int DT>
 __global__ __launch_bounds__(256) void render_range_kernel(const void* voxels, int dx, int dy, int dz, int lg, int nbx, int nby, float norm,
                                                            float offset, float one_minus_scaling, float2* range) {
-    typedef typename LinearLoad<DT>::T T;
+    typedef typename Voxel<DT>::T T;
     __shared__ float smin[kColumns + 1], smax[kColumns + 1];
     __shared__ int sbad[kColumns + 1];
     const int B = 1 << lg;
@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256) void render_range_kernel(const void* voxels, i
         int bad = 0;
         for (int z = z0; z <= z1; ++z)
             for (int y = y0; y <= y1; ++y) {
-                const float v = LinearLoad<DT>::widen(vox[(size_t)x + (size_t)dx * ((size_t)y + (size_t)dy * (size_t)z)]);
-                if (DT == CPM_F16 || DT == CPM_F32) bad |= !(__builtin_fabsf(v) < __builtin_inff());  // NaN or inf
+                const float v = Voxel<DT>::widen(vox[(size_t)x + (size_t)dx * ((size_t)y + (size_t)dy * (size_t)z)]);
+                if (Voxel<DT>::is_float) bad |= !(__builtin_fabsf(v) < __builtin_inff());  // NaN or inf
                 lo = min_(lo, v);  // (fminf / fmaxf drop a NaN; the brick is marked by `bad`)
                 hi = max_(hi, v);
             }
@@ -114,8 +114,7 @@ int cpm_render_accel_create(cpm_ctx* ctx, const cpm_volume_desc* desc, int brick
     if (brick <= 0) brick = 8;
     CPM_REQUIRE(ctx, brick == 4 || brick == 8 || brick == 16, "cpm_render_accel_create: brick must be 4, 8 or 16");
     CPM_REQUIRE(ctx, desc->dims[0] > 0 && desc->dims[1] > 0 && desc->dims[2] > 0, "cpm_render_accel_create: dims must be positive");
-    CPM_REQUIRE(ctx, desc->dtype == CPM_U8 || desc->dtype == CPM_U16 || desc->dtype == CPM_F16 || desc->dtype == CPM_F32 || desc->dtype == CPM_I16,
-                "cpm_render_accel_create: unknown voxel type");
+    CPM_REQUIRE(ctx, cpm_dtype_valid(desc->dtype), "cpm_render_accel_create: unknown voxel type");
     CPM_REQUIRE(ctx, (unsigned long long)desc->dims[0] * desc->dims[1] * desc->dims[2] < (1ull << 32), "cpm_render_accel_create: volume too large");
     cpm_render_accel* a = new cpm_render_accel();
     for (int i = 0; i < 3; ++i) a->dims[i] = desc->dims[i];
@@ -176,13 +175,7 @@ int cpm_render_accel_update(cpm_ctx* ctx, cpm_render_accel* accel, const cpm_vol
 #define CPM_RANGE_LAUNCH(DT)                                                                                                              \
     CPM_LAUNCH(ctx, (render_range_kernel<DT>), g, b, 0, s, (const void*)vol->voxels, accel->dims[0], accel->dims[1], accel->dims[2], accel->lg, \
                accel->nb[0], accel->nb[1], V.norm, V.offset, V.one_minus_scaling, accel->range)
-        switch (accel->dtype) {
-            case CPM_U8: CPM_RANGE_LAUNCH(CPM_U8); break;
-            case CPM_U16: CPM_RANGE_LAUNCH(CPM_U16); break;
-            case CPM_F16: CPM_RANGE_LAUNCH(CPM_F16); break;
-            case CPM_I16: CPM_RANGE_LAUNCH(CPM_I16); break;  // (w(v) is finite: never `bad`)
-            default: CPM_RANGE_LAUNCH(CPM_F32); break;
-        }
+        CPM_DISPATCH_DTYPE(accel->dtype, CPM_RANGE_LAUNCH);  // (I16: w(v) is finite, never `bad`)
 #undef CPM_RANGE_LAUNCH
         CPM_LAUNCH_CHECK(ctx, "render_range_kernel");
         accel->vol = vol;

@@ -189,13 +189,9 @@ int cpm_volume_mix(cpm_ctx* ctx, const cpm_volume* v0, const cpm_volume* v1, flo
     const uint4 *x = (const uint4*)v0->voxels, *y = (const uint4*)v1->voxels;
     uint4* o = (uint4*)out->voxels;
     int grid = stream_grid(ctx, n16);
-    switch (v0->desc.dtype) {
-        case CPM_U8: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_U8>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
-        case CPM_U16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_U16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
-        case CPM_F16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_F16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
-        case CPM_I16: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_I16>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
-        default: CPM_LAUNCH(ctx, volume_mix_kernel<CPM_F32>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o); break;
-    }
+#define CPM_MIX_LAUNCH(DT) CPM_LAUNCH(ctx, volume_mix_kernel<DT>, dim3(grid), dim3(256), 0, s, x, y, weight, n16, o)
+    CPM_DISPATCH_DTYPE(v0->desc.dtype, CPM_MIX_LAUNCH);
+#undef CPM_MIX_LAUNCH
     CPM_LAUNCH_CHECK(ctx, "volume_mix_kernel");
     // The tracer's footprint copy of the mixed volume is left to whoever needs it (cpm::trace_volume_source): a trace over all the
     // samples re-derives it first; the correlated update's re-traces of a few per cent of the photons read the linear block instead,

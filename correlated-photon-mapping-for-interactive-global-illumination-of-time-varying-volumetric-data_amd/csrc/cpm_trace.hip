@@ -211,9 +211,7 @@ void make_vol_dev(const cpm_volume* vol, tracer::VolDev& V) {
     V.sy = (uint32_t)d.dims[0];
     V.sz = (uint32_t)d.dims[0] * (uint32_t)d.dims[1];
     V.mul24 = V.sz < (1u << 24) && d.dims[0] < (1 << 24) && d.dims[1] < (1 << 24) && d.dims[2] < (1 << 24);
-    V.norm = d.dtype == CPM_U8 ? (1.0f / 255.0f) : (d.dtype == CPM_U16 ? (1.0f / 65535.0f) : 1.0f);  // (F16, F32, I16: 1)
-    V.offset = d.format_offset;
-    V.one_minus_scaling = 1.0f - d.format_scaling;
+    set_value_mapping(V, d);
 }
 
 int make_trace_args(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const cpm_tf* tf_scattering, const float aabb[8],
@@ -408,22 +406,8 @@ int trace_impl(cpm_ctx* ctx, const cpm_volume* vol, const cpm_tf* tf, const cpm_
         if (single) CPM_LAUNCH(ctx, (trace_kernel<DT, EMIT_NONE, true, false, true>), grid, block, lds, s, A);            \
         else CPM_LAUNCH(ctx, (trace_kernel<DT, EMIT_NONE, false, false, true>), grid, block, lds, s, A);                  \
     } while (0)
-    if (sel.lights) {
-        switch (d.dtype) {
-            case CPM_U8: CPM_TRACE_LAUNCH_MULTI(CPM_U8); break;
-            case CPM_U16: CPM_TRACE_LAUNCH_MULTI(CPM_U16); break;
-            case CPM_F16: CPM_TRACE_LAUNCH_MULTI(CPM_F16); break;
-            case CPM_I16: CPM_TRACE_LAUNCH_MULTI(CPM_I16); break;
-            default: CPM_TRACE_LAUNCH_MULTI(CPM_F32); break;
-        }
-    } else
-    switch (d.dtype) {
-        case CPM_U8: CPM_TRACE_LAUNCH(CPM_U8); break;
-        case CPM_U16: CPM_TRACE_LAUNCH(CPM_U16); break;
-        case CPM_F16: CPM_TRACE_LAUNCH(CPM_F16); break;
-        case CPM_I16: CPM_TRACE_LAUNCH(CPM_I16); break;
-        default: CPM_TRACE_LAUNCH(CPM_F32); break;
-    }
+    if (sel.lights) CPM_DISPATCH_DTYPE(d.dtype, CPM_TRACE_LAUNCH_MULTI);
+    else CPM_DISPATCH_DTYPE(d.dtype, CPM_TRACE_LAUNCH);
 #undef CPM_TRACE_LAUNCH_MULTI
 #undef CPM_TRACE_LAUNCH
 #undef CPM_TRACE_LAUNCH_E

@@ -3,7 +3,6 @@
 // (importance_retrace_kernel: detector + threshold + tracer in one launch).  Replaces photonTracerKernel
 // (ref progressivephotonmapping/cl/photontracer.cl:69-216) and woodcockTracking (ref cl/transmittance.cl:126-144).
 #pragma once
-#include <type_traits>
 #include "cpm_ctx.h"
 #include "cpm_emit.hip.h"
 
@@ -64,54 +63,20 @@ enum { EMIT_NONE = 0, EMIT_DIRECTIONAL = 1, EMIT_POINT = 2 };
 // { v(x, y, z), v(x, y + 1, z), v(x, y, z + 1), v(x, y + 1, z + 1) } (clamped at the last row / slice).  Four x-pair fetches of
 // the linear layout before: the texture-address path is the loop's second bottleneck; two fetches per sample took 10 % off the
 // config-2 trace and 24 % off a 33-step-per-photon one, one fetch a further 5 % and 13 %.
-template <int DT> struct FootprintLoad;
-template <> struct FootprintLoad<CPM_U8> {
+// The 1- and 2-byte types: the footprint's 8 or 16 bytes as 32-bit words, each texel shifted down, masked and widened
+// on its own (Voxel<DT>::widen, cpm_voxel.h) before the f32 path's lerps -- no packed arithmetic, so a sample of an F16 or I16 volume is
+// the bits of the F32 volume of the widened values.  u8: v_cvt_f32_ubyte0..3; binary16: v_cvt_f32_f16, the high halves through op_sel /
+// SDWA; int16: v_bfe_i32 / v_ashrrev, v_max_i32, v_cvt_f32_i32, v_mul_f32.
+template <int DT> struct FootprintLoad {
+    typedef typename Voxel<DT>::T T;
     static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
-        uint32_t w[2];
-        __builtin_memcpy(w, static_cast<const uint8_t*>(base) + 4 * (size_t)idx, 8);
+        constexpr int PER = 4 / Voxel<DT>::size, BITS = 8 * Voxel<DT>::size;  // texels per word, bits per texel
+        uint32_t w[8 / PER];
+        __builtin_memcpy(w, static_cast<const T*>(base) + 4 * (size_t)idx, sizeof(w));
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {  // v_cvt_f32_ubyte0..3
-            v[4 * i + 0] = (float)(w[i] & 0xffu);
-            v[4 * i + 1] = (float)((w[i] >> 8) & 0xffu);
-            v[4 * i + 2] = (float)((w[i] >> 16) & 0xffu);
-            v[4 * i + 3] = (float)(w[i] >> 24);
-        }
-    }
-};
-template <> struct FootprintLoad<CPM_U16> {
-    static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
-        uint32_t w[4];
-        __builtin_memcpy(w, static_cast<const uint16_t*>(base) + 4 * (size_t)idx, 16);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i + 0] = (float)(w[i] & 0xffffu);
-            v[2 * i + 1] = (float)(w[i] >> 16);
-        }
-    }
-};
-// binary16: the 2-byte footprint of u16, each texel widened on its own (v_cvt_f32_f16, the high halves through op_sel / SDWA) before
-// the f32 path's lerps -- no packed-f16 arithmetic, so a sample is the bits of the F32 volume of the widened values
-template <> struct FootprintLoad<CPM_F16> {
-    static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
-        uint32_t w[4];
-        __builtin_memcpy(w, static_cast<const uint16_t*>(base) + 4 * (size_t)idx, 16);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i + 0] = half_to_float(w[i]);
-            v[2 * i + 1] = half_to_float(w[i] >> 16);
-        }
-    }
-};
-// int16 (SNORM): the same 2-byte footprint, each texel normalised on its own (snorm16_to_float: v_bfe_i32 / v_ashrrev, v_max_i32,
-// v_cvt_f32_i32, v_mul_f32) before the f32 path's lerps -- a sample is the bits of the F32 volume of the normalised values
-template <> struct FootprintLoad<CPM_I16> {
-    static CPM_DEV void load(const void* base, uint32_t idx, float (&v)[8]) {
-        uint32_t w[4];
-        __builtin_memcpy(w, static_cast<const uint16_t*>(base) + 4 * (size_t)idx, 16);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i + 0] = snorm16_to_float(w[i]);
-            v[2 * i + 1] = snorm16_to_float(w[i] >> 16);
+        for (int i = 0; i < 8; ++i) {  // (a word's top texel by the bare shift: v_cvt_f32_ubyte3, op_sel on the high half)
+            const uint32_t t = w[i / PER] >> (BITS * (i % PER));
+            v[i] = Voxel<DT>::widen(i % PER == PER - 1 ? t : t & ((1u << BITS) - 1u));
         }
     }
 };
@@ -133,9 +98,7 @@ CPM_DEV void coord(float s, float dimf, float m1, float m2, float& fl, float& a)
 // The same eight voxels from the volume's linear block (x fastest): four fetches of an x-pair, rows (y, z), (y', z), (y, z'), (y', z')
 // with y' = min(y + 1, dim.y - 1), z' likewise -- exactly what a footprint element holds -- into the same order.
 template <int DT> struct LinearLoad {
-    typedef typename std::conditional<DT == CPM_U8, uint8_t,
-            typename std::conditional<DT == CPM_U16 || DT == CPM_F16 || DT == CPM_I16, uint16_t, float>::type>::type T;
-    static CPM_DEV float widen(T t) { return DT == CPM_F16 ? half_to_float(t) : DT == CPM_I16 ? snorm16_to_float(t) : (float)t; }
+    typedef typename Voxel<DT>::T T;
     static CPM_DEV void load(const VolDev& V, uint32_t b00, int iy, int iz, float (&v)[8]) {
         const T* base = static_cast<const T*>(V.voxels) + b00;
         const uint32_t up = (float)iy < V.my1 ? V.sy : 0u, back = (float)iz < V.mz1 ? V.sz : 0u;
@@ -144,7 +107,7 @@ template <int DT> struct LinearLoad {
         for (int k = 0; k < 4; ++k) {
             T pr[2];
             __builtin_memcpy(pr, base + off[k], sizeof(pr));
-            v[k] = widen(pr[0]); v[4 + k] = widen(pr[1]);
+            v[k] = Voxel<DT>::widen(pr[0]); v[4 + k] = Voxel<DT>::widen(pr[1]);
         }
     }
 };

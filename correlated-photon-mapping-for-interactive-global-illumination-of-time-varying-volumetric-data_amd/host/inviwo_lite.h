@@ -8,7 +8,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
-#include "cpm/cpm.h"  // cpm_dtype
+#include "cpm/cpm.h"  // cpm_dtype, cpm_dtype_size
 
 #include <array>
 #include <cmath>
@@ -135,7 +135,7 @@ public:
     size3_t getDimensions() const { return dims_; }
     void setDimensions(size3_t d) { dims_ = d; data.setSize(0); invalidateDeviceRepresentation(); }
     int dtype() const { return dtype_; }
-    size_t elementSize() const { return dtype_ == CPM_U8 ? 1 : (dtype_ == CPM_U16 || dtype_ == CPM_F16 || dtype_ == CPM_I16 ? 2 : 4); }
+    size_t elementSize() const { return cpm_dtype_size(dtype_); }
     // getDataFormat()->getString() of the scalar formats the path takes (cpm_dtype)
     const char* getDataFormatString() const {
         return dtype_ == CPM_U8 ? "UINT8" : dtype_ == CPM_U16 ? "UINT16" : dtype_ == CPM_F16 ? "FLOAT16" : dtype_ == CPM_I16 ? "INT16" : "FLOAT32";

@@ -460,4 +460,7 @@ int cpm_allreduce_grids(cpm_ctx* const* ctxs, cpm_comm* const* comms, float* con
 #ifdef __cplusplus
 }
 #endif
+
+#include "cpm_dtype.h" /* cpm_dtype_valid, cpm_dtype_size: inline, nothing exported */
+
 #endif /* CPM_CPM_H */

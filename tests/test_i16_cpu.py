@@ -101,6 +101,19 @@ def test_element_sizes(cpm):
     assert [lib.cpmh_volume_element_size(d) for d in (B.CPM_U8, B.CPM_U16, B.CPM_F32, B.CPM_F16)] == [1, 2, 4, 2]
 
 
+def test_the_bindings_one_table_agrees_with_numpy_and_the_host_layer(cpm):
+    """binding.VOXEL_TYPES (what DTYPE_SIZE and the dtype maps are derived from) against numpy's item sizes and cpm_dtype_size as the
+    host layer's Volume reports it"""
+    B = cpm.binding
+    assert [row[0] for row in B.VOXEL_TYPES] == [B.CPM_U8, B.CPM_U16, B.CPM_F32, B.CPM_F16, B.CPM_I16] == list(B.DTYPE_SIZE)
+    cpm.build.build_host_library()
+    lib = C.CDLL(str(B.LIB_PATH.parent / "libcpm_host.so"))
+    lib.cpmh_volume_element_size.argtypes = [C.c_int]
+    for code, np_name, torch_name, size in B.VOXEL_TYPES:
+        assert size == B.DTYPE_SIZE[code] == np.dtype(np_name).itemsize == lib.cpmh_volume_element_size(code)
+        assert B._np_dtype_code(np_name) == code and torch_name in (np_name, None)
+
+
 @pytest.mark.parametrize("dims", [(7, 9, 11), (24, 24, 24)])
 def test_i16_delta_decodes_to_the_exact_bytes(cpm, dims):
     """the delta encoder counts 2 bytes per I16 voxel: its runs rebuild the next step byte for byte"""
